@@ -20,9 +20,15 @@ composes the shards, and the index is exchanged by owner with xGMI peer
 copies (no RCCL).  Weak scaling; the call returns when every shard is done,
 so the step time is the max over shards by construction.
 
-Also prints: roofline of the dominant kernel (scan_kernel, HIP events on the
-library's stream) and a CPU baseline (oracle/, the C restatement of the
-reference path, timed on this host on rank 0 at N=1).
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the result line: the headline figure and the roofline of the
+dominant kernel from the HIP events the timed steps themselves stamped
+(scan_kernel, on the library's stream).  `--dump-outputs DIR` also writes what
+the last timed step returned (dump_result).  Everything that takes runs of its
+own is behind `--full`: the in-run streaming ceiling (roofline.peak_measured)
+and the CPU baseline (oracle/, the C restatement of the reference path, timed
+on this host on rank 0 at N=1).  The other workloads (`--config`) are chosen
+by name and report as before.
 """
 from __future__ import annotations
 
@@ -61,6 +67,52 @@ def kernel_sources_hash() -> str:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()
+
+
+DUMP_SAMPLE = 1 << 15  # elements kept of every result array longer than this
+DUMP_SEED = 0x5EED0D0D
+# srd_device_result's arrays: (field, element type, the field holding its length)
+RESULT_ARRAYS = (("meta_off", np.uint64, "n_chain"), ("key_hash", np.uint64, "n_chain"),
+                 ("prev_offset", np.uint64, "n_chain"), ("payload_start", np.uint64, "n_chain"),
+                 ("payload_len", np.uint64, "n_chain"), ("crc_stored", np.uint32, "n_chain"),
+                 ("crc_computed", np.uint32, "n_chain"), ("crc_ok", np.uint8, "n_chain"),
+                 ("index_key_hash", np.uint64, "n_index"), ("index_packed", np.uint64, "n_index"))
+
+
+def dump_sample(n: int) -> np.ndarray:
+    """The positions kept of an n-element array: all of them up to DUMP_SAMPLE,
+    else a fixed seeded sample (the same for every run and build), ascending."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False)).astype(np.int64)
+
+
+def dump_result(d: str, r, device: int, suffix: str = "") -> None:
+    """--dump-outputs: the arrays a caller of the timed call receives (the
+    srd_device_result `r` of the last timed step, still in HBM), as float64
+    `d/<field><suffix>.npy`.  Chain arrays are in the library's order (file
+    order); the index, whose order the ABI leaves open, is sorted by key hash.
+    Of arrays longer than DUMP_SAMPLE the positions dump_sample() picks are
+    kept.  A u64 array is written as (k, 2) = (high, low) 32-bit halves, exact
+    in float64.  `sums<suffix>.npy` holds, in RESULT_ARRAYS order, the sum of
+    ALL elements of each array modulo 2^32, so that a difference outside the
+    sample still shows."""
+    order = None
+    sums = []
+    for name, dt, cnt in RESULT_ARRAYS:
+        n = int(getattr(r, cnt))
+        t = S.device_view(getattr(r, name), n, dt, device)
+        sums.append(float(int(t.sum(dtype=torch.int64).item()) & 0xFFFFFFFF))
+        if cnt == "n_index":
+            if order is None:
+                order = torch.argsort(S.device_view(r.index_key_hash, n, np.uint64, device))
+            t = t[order]
+        keep = torch.from_numpy(dump_sample(n)).to(t.device)
+        a = t[keep].cpu().numpy().view(dt)
+        if dt is np.uint64:
+            a = np.stack([a >> np.uint64(32), a & np.uint64(0xFFFFFFFF)], axis=1)
+        np.save(os.path.join(d, f"{name}{suffix}.npy"), a.astype(np.float64))
+    np.save(os.path.join(d, f"sums{suffix}.npy"), np.array(sums, np.float64))
 
 
 def algorithmic_bytes(n_entries: int, payload: int) -> int:
@@ -260,9 +312,16 @@ def bench_c5(args, ctx, local):
     assert torch.equal(out[:size], store[:size]), "C5 output differs from the C2 store"
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        appended = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:  # what the last timed call returned and wrote: the appended length, the sum of the
+        # store's bytes modulo 2^32, and a seeded sample of the bytes
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        keep = torch.from_numpy(dump_sample(size)).to(dev)
+        np.save(os.path.join(args.dump_outputs, "store_bytes.npy"), out[keep].cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "summary.npy"),
+                np.array([appended, int(out[:size].sum(dtype=torch.int64).item()) & 0xFFFFFFFF], np.float64))
     # the writer kernel alone, inputs resident in HBM (layout from srd_batch_layout)
     ents = (S.WriteEntry * n)()
     nt = C.c_uint64()
@@ -412,7 +471,16 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--e2e", action="store_true", help="also time host->HBM->result end to end (stderr)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the in-run streaming ceiling (roofline.peak_measured, "
+                         "frac_measured) and, at N=1 on c2, the CPU baseline (--no-cpu leaves that out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (dump_result)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.config == "ops":
+        ap.error("--dump-outputs: --config ops times several calls, not one path")
 
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -468,8 +536,11 @@ def main():
 
         vflags = S.SRD_FLAG_FORCE_FULL if full else 0
 
+        last = None  # the srd_device_result of the latest step (--dump-outputs)
+
         def step():
-            r = S.validate_index_device(store.data_ptr(), flen, vflags, ctx)
+            nonlocal last
+            last = r = S.validate_index_device(store.data_ptr(), flen, vflags, ctx)
             return r.final_len, r.n_chain, r.n_crc_bad, r.n_index, r.mode
         expect = (size, n, 0, n, S.SRD_MODE_FULL if full else S.SRD_MODE_OPTIMISTIC)
     else:
@@ -519,7 +590,7 @@ def main():
 
     for _ in range(args.warmup):
         got = step()
-    assert got == expect, (got, expect)
+        assert got == expect, (got, expect)
 
     for d in set(devs):
         torch.cuda.synchronize(d)
@@ -531,7 +602,7 @@ def main():
         c.set_timing_every(scan_sample(args.steps))  # restarts the sample: timed steps 0, k, 2k, ...
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        got = step()
         if multi is not None:
             for k in ("validate_ms", "exchange_ms", "total_ms"):
                 multi[k] += getattr(summ, k)
@@ -539,6 +610,17 @@ def main():
     for d in set(devs):
         torch.cuda.synchronize(d)
     dt = time.perf_counter() - t0
+    assert got == expect, (got, expect)
+    if args.dump_outputs:
+        # the last timed step's result, before any further call on the
+        # contexts reuses the workspace its arrays live in
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "summary.npy"), np.array(got, np.float64))
+        if multi is None:
+            dump_result(args.dump_outputs, last, local)
+        else:
+            for i in range(world):
+                dump_result(args.dump_outputs, res[i], devs[i], f"_shard{i}")
     scan_ms_sum, scan_n, _ = ctx.timings()
     shard_ms = None
     if multi is not None:
@@ -547,8 +629,9 @@ def main():
         shard_ms = [round(buf[i], 4) for i in range(min(k, world))]
     # the streaming-read ceiling of the scan's geometry on these very bytes,
     # after the timed region (the measured stream-read peak)
-    probe_bytes = (flen if multi is None else cuts[1] - soffs[0]) // 4096 * 4096
-    probe_best, probe_med = S.stream_probe_device(store.data_ptr(), probe_bytes, PROBE_REPS, ctx)
+    if args.full:
+        probe_bytes = (flen if multi is None else cuts[1] - soffs[0]) // 4096 * 4096
+        probe_best, probe_med = S.stream_probe_device(store.data_ptr(), probe_bytes, PROBE_REPS, ctx)
     scan_each = sorted(ctx.scan_list())  # the sampled timed steps' scan durations (ms), one per launch
     if multi is not None:
         multi["scan_ms"] = [(scan_ms_sum, scan_n)] + [c.timings()[:2] for c in ctxs[1:]]
@@ -627,16 +710,6 @@ def main():
             "peak": HBM_PEAK_GBS,
             "unit": "GB/s",
             "frac": round(achieved / HBM_PEAK_GBS, 4),
-            # the measured ceiling: srd_stream_probe_device streams the same
-            # store with the scan's geometry (one 16-wave block per CU, 64 B
-            # per lane, 3-deep ring) and does nothing with the bytes, best of
-            # PROBE_REPS runs in this process.  peak_measured = file bytes /
-            # probe ms; frac_measured = probe ms / scan ms (the scan against
-            # streaming alone, in algorithmic bytes: both read the same file)
-            "peak_measured": round(probe_bytes / (probe_best * 1e-3) / 1e9, 1),
-            "probe_ms_best": round(probe_best, 4),
-            "probe_ms_median": round(probe_med, 4),
-            "frac_measured": round(probe_best / scan_ms, 4),
             "traffic": traffic,
             "traffic_note": traffic_note,
             # the whole step (scan + glue + one host sync) against the same peak
@@ -666,7 +739,20 @@ def main():
         out["roofline"]["scan_loads"] = {0: "coalesced + transpose", 1: "line per lane"}.get(ctx.scan_loads(), "none")
         _, t_co, t_li = ctx.scan_trial()  # the trial's fastest device-timed scan per pattern (srd_ctx_scan_trial)
         out["roofline"]["scan_loads_trial_ms"] = {"coalesced": round(t_co, 4), "lines": round(t_li, 4)}
-    if world == 1 and not args.no_cpu and args.config == "c2":
+    if args.full:
+        # the measured ceiling: srd_stream_probe_device streams the same
+        # store with the scan's geometry (one 16-wave block per CU, 64 B
+        # per lane, 3-deep ring) and does nothing with the bytes, best of
+        # PROBE_REPS runs in this process.  peak_measured = file bytes /
+        # probe ms; frac_measured = probe ms / scan ms (the scan against
+        # streaming alone, in algorithmic bytes: both read the same file)
+        out["roofline"].update({
+            "peak_measured": round(probe_bytes / (probe_best * 1e-3) / 1e9, 1),
+            "probe_ms_best": round(probe_best, 4),
+            "probe_ms_median": round(probe_med, 4),
+            "frac_measured": round(probe_best / scan_ms, 4),
+        })
+    if args.full and world == 1 and not args.no_cpu and args.config == "c2":
         out["cpu_baseline"] = cpu_baseline(store, size, bytes_alg, args.cpu_budget)
     if args.e2e and world == 1:
         out_e2e = e2e(store, size, bytes_alg, ctx)

@@ -2,7 +2,7 @@
 #   bash tools/gpu.sh STEP [STEP ...]     run on the box: gpurun -- 'bash tools/gpu.sh tests bench prof'
 # Steps (each under its own time limit; the first failure ends the call):
 #   tests        pytest -m gpu ($PYTEST_TARGETS, default: tests)   smoke   __graft_entry__.smoke()
-#   bench        python bench.py $BENCH_ARGS           prof    rocprofv3 kernel stats of a 20-step bench
+#   bench        python bench.py --full $BENCH_ARGS    prof    rocprofv3 kernel stats of a 20-step bench
 #   pmc          the standard PMC passes + traffic     pmcx    one extra PMC pass: counters in $PMC
 #   list         rocprofv3 -L (available counters)     ab      python $AB (an A/B timing tool) $AB_ARGS
 #   pmcab        one PMC pass ($PMC) over python $AB $AB_ARGS
@@ -23,10 +23,13 @@ for step in "$@"; do
       || { echo SMOKE_FAIL; tail -30 gpurun_out/smoke_$TAG.log; exit 1; }
     cat gpurun_out/smoke_$TAG.log ;;
   bench)
+    # the recorded line carries the whole report (streaming ceiling, CPU baseline): bench.py --full
+    BENCH_ARGS="--full ${BENCH_ARGS#--full }"
     timeout -k 10 300 python bench.py ${BENCH_ARGS} > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err \
       || { echo BENCH_FAIL; tail -30 gpurun_out/bench_$TAG.err; exit 1; }
     cut -c1-900 gpurun_out/bench_$TAG.json ;;
   prof)
+    BENCH_ARGS="${BENCH_ARGS#--full }"  # a plain run: the timed steps' kernels only
     rm -rf gpurun_out/prof_$TAG
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$TAG -o run -- \
       python3 bench.py --no-cpu --steps 20 ${BENCH_ARGS} > gpurun_out/bench_prof_$TAG.log 2>&1 \
@@ -40,10 +43,12 @@ for r in csv.DictReader(open('gpurun_out/kernel_stats_$TAG.csv')):
     t=$(find gpurun_out/prof_$TAG -name '*kernel_trace.csv' | head -1)
     python3 tools/trace_gaps.py "$t" 2 > gpurun_out/trace_gaps_$TAG.txt; tail -12 gpurun_out/trace_gaps_$TAG.txt ;;
   pmc)
+    BENCH_ARGS="${BENCH_ARGS#--full }"
     bash tools/gpu_pmc.sh > gpurun_out/pmc_summary_$TAG.txt 2>&1 || { echo PMC_FAIL; tail -20 gpurun_out/pmc_summary_$TAG.txt; exit 1; }
     head -32 gpurun_out/pmc_summary_$TAG.txt
     python3 tools/traffic_json.py gpurun_out/pmc_c gpurun_out/pmc_d gpurun_out/traffic_$TAG.json || { echo TRAFFIC_FAIL; exit 1; } ;;
   pmcx)
+    BENCH_ARGS="${BENCH_ARGS#--full }"
     rm -rf gpurun_out/pmc_x_$TAG
     timeout -s KILL 120 rocprofv3 --pmc ${PMC} --output-format csv -d gpurun_out/pmc_x_$TAG -o run -- \
       python3 bench.py --steps 3 --warmup 1 --no-cpu ${BENCH_ARGS} > gpurun_out/pmc_x_$TAG.log 2>&1 \
