@@ -109,8 +109,9 @@ int srd_ctx_scan_loads(srd_ctx *ctx);
  * (or pinned by SRD_SCAN_LOADS, or with XCD-aware shares off). */
 int srd_ctx_scan_trial(srd_ctx *ctx, double *ms);
 const char *srd_last_error(void);
-/* The sha256 of the sources this library was compiled from (csrc/ +
- * include/srd_amd.h, rust-simd-r-drive_amd/src_hash.py), 64 hex digits;
+/* The sha256 of the sources this library was compiled from (every .hip / .h /
+ * .cpp file under csrc/ and include/srd_amd.h, as computed by
+ * rust-simd-r-drive_amd/src_hash.py, which is not itself hashed), 64 hex digits;
  * the Python mirror refuses a library whose hash differs from the sources
  * beside it, and bench.py / smoke print it. */
 const char *srd_build_info(void);

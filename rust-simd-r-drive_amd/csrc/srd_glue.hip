@@ -1,5 +1,6 @@
 // srd_glue.hip -- sync-free glue of the optimistic pass (included by srd_api.hip
-// after srd_kernels.hip).
+// after srd_kernels.hip; its host side is srd_validate.hip, the index build's
+// srd_index_build.hip).
 //
 // Everything between the streaming scan and the final result runs with the
 // counts kept in device memory (struct Plan); the host enqueues the pass and
@@ -1280,6 +1281,22 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_finalize_kernel(ShapeArgs
 // --------------------------------------------------------------------------
 // KeyIndexer::build, bucketed
 // --------------------------------------------------------------------------
+// a stand-alone build's first launch: zeroes the plan and the bucket fills
+// and sets the pair count, from the host (n) or from the device (*d_n)
+__global__ void index_prep_kernel(Plan* pl, uint64_t n, uint32_t* zero, uint32_t nz) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nz) zero[i] = 0;
+  if (i < sizeof(Plan) / 4) ((uint32_t*)pl)[i] = 0;
+  __syncthreads();
+  if (i == 0) pl->n_chain = n;
+}
+__global__ void index_prep_dev_kernel(Plan* pl, const uint64_t* d_n, uint32_t* zero, uint32_t nz) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nz) zero[i] = 0;
+  if (i < sizeof(Plan) / 4) ((uint32_t*)pl)[i] = 0;
+  __syncthreads();
+  if (i == 0) pl->n_chain = *d_n;
+}
 // KeyIndexer::build's bucketing in one launch: each block histograms its chunk in LDS, claims its
 // ranges of the buckets (one atomicAdd per bucket) and scatters the chunk --
 // no per-(block, bucket) base table in HBM and the keys read once more from

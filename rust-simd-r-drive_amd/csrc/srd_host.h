@@ -1,6 +1,7 @@
 // srd_host.h -- host-only parsing of untrusted store bytes (no HIP).
 //
-// Compiled into libsrd_amd.so (through srd_api.hip) and, on its own with
+// Compiled into libsrd_amd.so (srd_api.hip, the one translation unit,
+// includes srd_host.cpp) and, on its own with
 // -fsanitize=address,undefined, into the sanitizer harness
 // (tests/sanitize/host_fuzz.cpp): everything here reads file bytes the
 // caller does not vouch for, so it must stay in bounds for any input.

@@ -842,7 +842,7 @@ void scan_kernel(ScanArgs a) {
   constexpr int NW = SCAN_WAVES_V2;
   // The product loads each tile coalesced + nontemporal and transposes it in
   // registers (coal_to_lines); SCAN_LINES = round 4's line-per-lane loads
-  // (the pass measures both per store: srd_api.hip scan_variant_tune).  Timing-only
+  // (the pass measures both per store: srd_scan_host.hip scan_variant_tune).  Timing-only
   // ablations of SRD_DEBUG_API builds (results wrong; tools/variant_ab.py):
   // 7 = the ring's coalesced loads alone (each tile XOR-folded), 8 = the whole
   // coalesced tile body on two L2-resident tiles per block (no HBM stream).
@@ -1761,6 +1761,27 @@ __global__ void remap_kernel(const uint64_t* vlist, const uint64_t* nv, const in
   int64_t vp = p >= 0 ? (int64_t)vpos[p] : p;
   vpar[i] = vp;
   vslot[i] = slot[g];
+}
+// the valid nodes in dense order from the exclusive scan of their flags:
+// vlist[pos] = g, vpos[g] = pos, and their count
+__global__ void compact_valid_kernel(const uint32_t* vflag, const uint32_t* vscan, uint64_t K, uint64_t* vlist,
+                                     uint64_t* vpos, uint64_t* nv) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= K) return;
+  const uint32_t pos = vscan[g], f = vflag[g];
+  if (f) {
+    vlist[pos] = g;
+    vpos[g] = pos;
+  }
+  if (g == K - 1) *nv = (uint64_t)pos + (f ? 1 : 0);
+}
+// the walk starts at node g's compacted position
+__global__ void walk_start_kernel(WalkState* ws, const uint64_t* vpos, uint64_t g) {
+  if (threadIdx.x == 0) {
+    WalkState w{};
+    w.start = vpos[g];
+    *ws = w;
+  }
 }
 
 // --------------------------------------------------------------------------

@@ -1,0 +1,511 @@
+// srd_ops.hip -- host launch code of the remaining kernel families (included
+// by srd_api.hip): stream probe, batch digests, synth, batch writer, device
+// lookup table and batched reads, iterator and compaction.
+extern "C" int srd_stream_probe_device(srd_ctx* c, const uint8_t* d_buf, uint64_t bytes, int reps, double* best_ms,
+                                       double* median_ms) {
+  if (!c || !d_buf || bytes < TILE || reps < 1 || !best_ms) { set_err("bad argument"); return SRD_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  const uint64_t ntiles = bytes / TILE;
+  TRY(ensure(c, B_PROBE, (uint64_t)c->scan_blocks * 16 * 4));
+  hipEvent_t e[2];
+  for (auto& x : e) HIPCHK(hipEventCreateWithFlags(&x, hipEventReleaseToDevice));
+  std::vector<float> ms;
+  int rc = 0;
+  for (int r = 0; r < reps + 1 && !rc; r++) {  // (the first run warms the code and the TLB)
+    hipExtLaunchKernelGGL(stream_probe_kernel, dim3(c->scan_blocks), dim3(1024), 0, c->stream, e[0], e[1], 0, d_buf,
+                          ntiles, P<uint32_t>(c, B_PROBE));
+    float t = 0;
+    if (hipGetLastError() != hipSuccess || hipEventSynchronize(e[1]) != hipSuccess ||
+        hipEventElapsedTime(&t, e[0], e[1]) != hipSuccess) {
+      set_err("stream probe launch failed");
+      rc = SRD_ERR_HIP;
+    }
+    if (r) ms.push_back(t);
+  }
+  for (auto& x : e) hipEventDestroy(x);
+  if (rc) return rc;
+  std::sort(ms.begin(), ms.end());
+  *best_ms = ms[0];
+  if (median_ms) *median_ms = ms[ms.size() / 2];
+  return 0;
+}
+
+extern "C" int srd_crc32_batch_device(srd_ctx* c, const uint8_t* d_buf, const uint64_t* d_offs,
+                                      const uint64_t* d_lens, uint64_t n, uint32_t* d_out, void* stream) {
+  if (!c) { set_err("bad argument"); return SRD_ERR_ARG; }
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if (!n) return 0;
+  crc_batch_kernel<<<(unsigned)std::min<uint64_t>(n, 8192), 64, 0, s>>>(d_buf, d_offs, d_lens, n, d_out);
+  KCHK(c, "crc_batch_kernel");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int srd_xxh3_64_batch_device(srd_ctx* c, const uint8_t* d_keys, const uint64_t* d_offs,
+                                        const uint64_t* d_lens, uint64_t n, uint64_t* d_out, void* stream) {
+  if (!c) { set_err("bad argument"); return SRD_ERR_ARG; }
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if (!n) return 0;
+  xxh3_batch_kernel<<<blocks(n, 256), 256, 0, s>>>(d_keys, d_offs, d_lens, n, d_out);
+  KCHK(c, "xxh3_batch_kernel");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+template <class OUT, class F>
+static int batch_host(srd_ctx* c, const uint8_t* buf, uint64_t blen, const uint64_t* offs, const uint64_t* lens,
+                      uint64_t n, OUT* out, F launch) {
+  HIPCHK(hipSetDevice(c->device));
+  for (uint64_t i = 0; i < n; i++)
+    if (offs[i] > blen || lens[i] > blen - offs[i]) { set_err("range out of bounds"); return SRD_ERR_ARG; }
+  void *db = nullptr, *dof = nullptr, *dl = nullptr, *dout = nullptr;
+  HIPCHK(hipMalloc(&db, blen + 1));
+  HIPCHK(hipMalloc(&dof, n * 8 + 8));
+  HIPCHK(hipMalloc(&dl, n * 8 + 8));
+  HIPCHK(hipMalloc(&dout, n * sizeof(OUT) + 8));
+  if (blen) HIPCHK(hipMemcpyAsync(db, buf, blen, hipMemcpyHostToDevice, c->stream));
+  if (n) {
+    HIPCHK(hipMemcpyAsync(dof, offs, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dl, lens, n * 8, hipMemcpyHostToDevice, c->stream));
+  }
+  int r = launch((const uint8_t*)db, (const uint64_t*)dof, (const uint64_t*)dl, (OUT*)dout);
+  if (!r && n) HIPCHK(hipMemcpyAsync(out, dout, n * sizeof(OUT), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(spin_sync(c->stream));
+  hipFree(db); hipFree(dof); hipFree(dl); hipFree(dout);
+  return r;
+}
+
+extern "C" int srd_crc32_batch(srd_ctx* c, const uint8_t* buf, uint64_t blen, const uint64_t* offs,
+                               const uint64_t* lens, uint64_t n, uint32_t* out) {
+  if (!c || (n && (!offs || !lens || !out))) { set_err("bad argument"); return SRD_ERR_ARG; }
+  return batch_host<uint32_t>(c, buf, blen, offs, lens, n, out, [&](auto db, auto dof, auto dl, auto dout) {
+    return srd_crc32_batch_device(c, db, dof, dl, n, dout, nullptr);
+  });
+}
+
+extern "C" int srd_xxh3_64_batch(srd_ctx* c, const uint8_t* keys, uint64_t klen, const uint64_t* offs,
+                                 const uint64_t* lens, uint64_t n, uint64_t* out) {
+  if (!c || (n && (!offs || !lens || !out))) { set_err("bad argument"); return SRD_ERR_ARG; }
+  return batch_host<uint64_t>(c, keys, klen, offs, lens, n, out, [&](auto db, auto dof, auto dl, auto dout) {
+    return srd_xxh3_64_batch_device(c, db, dof, dl, n, dout, nullptr);
+  });
+}
+
+// entry tails: lens (if given) holds the lengths of entries 0 .. first+n-1
+static int synth_offsets(uint64_t first, uint64_t n, uint64_t fixed_len, const uint64_t* lens, uint64_t span_off,
+                         std::vector<uint64_t>* off, uint64_t* e0, uint64_t* lo, uint64_t* hi) {
+  uint64_t tail = 0;
+  *lo = 0;
+  *e0 = first;
+  bool have_e0 = false;
+  if (off) off->clear();
+  for (uint64_t i = 0; i < first + n; i++) {
+    const uint64_t L = lens ? lens[i] : fixed_len;
+    if (L == 0) { set_err("empty payload"); return SRD_ERR_ARG; }
+    if (i == first) *lo = tail;
+    const uint64_t end = tail + ((64 - tail % 64) & 63) + L + 20;
+    if (!have_e0 && (end > span_off || i == first)) { *e0 = i; have_e0 = true; }
+    if (have_e0 && off) off->push_back(tail);
+    tail = end;
+  }
+  *hi = tail;
+  return 0;
+}
+
+static int synth_launch(Ctx* c, uint8_t* d_abs, const std::vector<uint64_t>& off, uint64_t e0, uint64_t fixed_len,
+                        const uint64_t* lens, uint64_t seed, uint64_t clip_lo) {
+  const uint64_t n = off.size();
+  if (!n) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  void *doff = nullptr, *dl = nullptr;
+  HIPCHK(hipMalloc(&doff, n * 8));
+  HIPCHK(hipMemcpyAsync(doff, off.data(), n * 8, hipMemcpyHostToDevice, c->stream));
+  if (lens) {
+    HIPCHK(hipMalloc(&dl, n * 8));
+    HIPCHK(hipMemcpyAsync(dl, lens + e0, n * 8, hipMemcpyHostToDevice, c->stream));
+  }
+  synth_kernel<<<(unsigned)std::min<uint64_t>(n, 65536), 64, 0, c->stream>>>(
+      d_abs, (const uint64_t*)doff, (const uint64_t*)dl, fixed_len, n, seed, e0, clip_lo);
+  KCHK(c, "synth_kernel");
+  HIPCHK(hipGetLastError());
+  HIPCHK(spin_sync(c->stream));
+  hipFree(doff);
+  if (dl) hipFree(dl);
+  return 0;
+}
+
+extern "C" int srd_synth_store_device(srd_ctx* c, uint8_t* d_out, uint64_t n, uint64_t fixed_len,
+                                      const uint64_t* lens, uint64_t seed, uint64_t* len_out) {
+  if (!len_out) { set_err("bad argument"); return SRD_ERR_ARG; }
+  std::vector<uint64_t> off;
+  uint64_t e0, lo, hi;
+  TRY(synth_offsets(0, n, fixed_len, lens, 0, d_out ? &off : nullptr, &e0, &lo, &hi));
+  *len_out = hi;
+  if (!d_out || !n) return 0;
+  if (!c) { set_err("bad argument"); return SRD_ERR_ARG; }
+  return synth_launch(c, d_out, off, 0, fixed_len, lens, seed, 0);
+}
+
+extern "C" int srd_synth_span_device(srd_ctx* c, uint8_t* d_span, uint64_t span_off, uint64_t first,
+                                     uint64_t n, uint64_t fixed_len, const uint64_t* lens, uint64_t seed,
+                                     uint64_t* lo_out, uint64_t* hi_out) {
+  if (!lo_out || !hi_out || (span_off % SPAN_BYTES)) { set_err("bad argument"); return SRD_ERR_ARG; }
+  std::vector<uint64_t> off;
+  uint64_t e0, lo, hi;
+  TRY(synth_offsets(first, n, fixed_len, lens, span_off, d_span ? &off : nullptr, &e0, &lo, &hi));
+  *lo_out = lo;
+  *hi_out = hi;
+  if (!d_span || !n) return 0;
+  if (!c || span_off > lo) { set_err("bad argument: span_off must be <= the shard's lower tail"); return SRD_ERR_ARG; }
+  return synth_launch(c, d_span - span_off, off, e0, fixed_len, lens, seed, span_off);
+}
+
+// ---------------------------------------------------------------------------
+// Checksum-on-append batch writer (C5): layout on the host (prepad_len chains
+// every start to all earlier lengths), serialization + CRC + key hash on the
+// device (write_kernel), chunked H2D of the inputs on a side stream.
+extern "C" int srd_batch_layout(uint64_t tail, const uint8_t* payloads, const uint64_t* key_offs,
+                                const uint64_t* key_lens, const uint64_t* pay_offs, const uint64_t* pay_lens,
+                                uint64_t n, uint32_t flags, srd_write_entry* out, uint64_t* new_tail) {
+  const char* why = "";
+  const int r = srd_host::batch_layout(tail, payloads, key_offs, key_lens, pay_offs, pay_lens, n, flags, out, new_tail,
+                                       &why);
+  if (r) set_err(why);
+  return r;
+}
+
+static int launch_write(Ctx* c, hipStream_t s, const uint8_t* pay, const uint8_t* keys, const srd_write_entry* ent,
+                        uint64_t n, uint8_t* out, uint64_t base, uint64_t* kh, uint64_t* mo,
+                        unsigned int* null_only = nullptr) {
+  if (!n) return 0;
+  WriteArgs w{pay, keys, ent, n, out, base, kh, mo, null_only};
+  const unsigned g = (unsigned)std::min<uint64_t>((n + SCAN_WAVES_V2 - 1) / SCAN_WAVES_V2, c->scan_blocks);
+#ifdef SRD_DEBUG_API
+  if (c->scan_variant == 21)
+    write_kernel<1><<<g, SCAN_WAVES_V2 * 64, 0, s>>>(w);
+  else if (c->scan_variant == 22)
+    write_kernel<2><<<g, SCAN_WAVES_V2 * 64, 0, s>>>(w);
+  else if (c->scan_variant == 29)
+    write_kernel<9><<<g, SCAN_WAVES_V2 * 64, 0, s>>>(w);
+  else
+#endif
+    write_kernel<<<g, SCAN_WAVES_V2 * 64, 0, s>>>(w);
+  HIPCHK(hipGetLastError());
+  if (sync_debug()) {
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
+}
+
+extern "C" int srd_batch_write_device(srd_ctx* c, const uint8_t* d_keys, const uint8_t* d_payloads,
+                                      const srd_write_entry* d_entries, uint64_t n, uint8_t* d_out,
+                                      uint64_t out_base, uint64_t* d_kh_out, uint64_t* d_mo_out, void* stream) {
+  if (!c || (out_base & 63) ||
+      (n && (!d_keys || !d_payloads || !d_entries || !d_out || !d_kh_out || !d_mo_out))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  return launch_write(c, stream ? (hipStream_t)stream : c->stream, d_payloads, d_keys, d_entries, n, d_out, out_base,
+                      d_kh_out, d_mo_out);
+}
+
+extern "C" int srd_batch_write(srd_ctx* c, uint64_t tail, const uint8_t* keys, const uint64_t* key_offs,
+                               const uint64_t* key_lens, const uint8_t* payloads, const uint64_t* pay_offs,
+                               const uint64_t* pay_lens, uint64_t n, uint32_t flags, uint8_t* d_out, uint64_t out_cap,
+                               uint64_t* new_tail, uint64_t* kh_out, uint64_t* mo_out) {
+  if (!c || !new_tail || (n && (!payloads || !keys))) { set_err("bad argument"); return SRD_ERR_ARG; }
+  std::vector<srd_write_entry> E(n);
+  uint64_t nt = 0;
+  TRY(srd_batch_layout(tail, payloads, key_offs, key_lens, pay_offs, pay_lens, n, flags, E.data(), &nt));
+  *new_tail = nt;
+  if (!d_out || !n) return 0;
+  const uint64_t base = tail & ~63ull;
+  if (nt - base > out_cap) { set_err("out_cap too small for the batch"); return SRD_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  constexpr uint64_t CH = 64ull << 20;  // payload bytes per chunk (double-buffered in HBM)
+  constexpr uint64_t KCH = 8ull << 20;  // key bytes per chunk
+  constexpr uint64_t ENT_MAX = 1u << 16;
+  if (!c->cstream) {
+    HIPCHK(hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
+    for (int i = 0; i < 2; i++) {
+      HIPCHK(hipEventCreateWithFlags(&c->wev_copied[i], hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&c->wev_done[i], hipEventDisableTiming));
+      HIPCHK(hipHostMalloc(&c->pin_ent[i], ENT_MAX * sizeof(srd_write_entry), hipHostMallocDefault));
+    }
+  }
+  TRY(ensure(c, B_WKH, n * 8));
+  TRY(ensure(c, B_WMO, n * 8));
+  uint64_t* kh_dev = P<uint64_t>(c, B_WKH);
+  uint64_t* mo_dev = P<uint64_t>(c, B_WMO);
+  uint64_t e0 = 0;
+  for (int ci = 0; e0 < n; ci++) {
+    // a chunk: consecutive entries whose payload and key source ranges stay
+    // within CH / KCH (one entry at least); the ranges are copied as they lie
+    uint64_t plo = E[e0].src, phi = E[e0].src + E[e0].len;
+    uint64_t klo = E[e0].key_src, khi = klo + E[e0].key_len;
+    uint64_t e1 = e0 + 1;
+    while (e1 < n && e1 - e0 < ENT_MAX) {
+      const uint64_t pl2 = std::min(plo, E[e1].src), ph2 = std::max(phi, E[e1].src + E[e1].len);
+      const uint64_t kl2 = std::min(klo, E[e1].key_src), kh2 = std::max(khi, E[e1].key_src + E[e1].key_len);
+      if (ph2 - (pl2 & ~15ull) > CH || kh2 - kl2 > KCH) break;
+      plo = pl2; phi = ph2; klo = kl2; khi = kh2;
+      e1++;
+    }
+    const uint64_t pa = plo & ~15ull;  // keeps every source's 16-byte alignment in the staging buffer
+    const int slot = ci & 1;
+    if (ci >= 2) HIPCHK(hipEventSynchronize(c->wev_done[slot]));  // chunk ci-2's kernel has released the slot
+    TRY(ensure(c, (BufId)(B_WPAY0 + slot), phi - pa));
+    TRY(ensure(c, (BufId)(B_WKEY0 + slot), std::max<uint64_t>(khi - klo, 1)));
+    TRY(ensure(c, (BufId)(B_WENT0 + slot), ENT_MAX * sizeof(srd_write_entry)));
+    srd_write_entry* pe = (srd_write_entry*)c->pin_ent[slot];
+    for (uint64_t i = e0; i < e1; i++) {
+      pe[i - e0] = E[i];
+      pe[i - e0].src -= pa;
+      pe[i - e0].key_src -= klo;
+    }
+    HIPCHK(hipMemcpyAsync(P<void>(c, (BufId)(B_WPAY0 + slot)), payloads + pa, phi - pa, hipMemcpyHostToDevice,
+                          c->cstream));
+    if (khi > klo)
+      HIPCHK(hipMemcpyAsync(P<void>(c, (BufId)(B_WKEY0 + slot)), keys + klo, khi - klo, hipMemcpyHostToDevice,
+                            c->cstream));
+    HIPCHK(hipMemcpyAsync(P<void>(c, (BufId)(B_WENT0 + slot)), pe, (e1 - e0) * sizeof(srd_write_entry),
+                          hipMemcpyHostToDevice, c->cstream));
+    HIPCHK(hipEventRecord(c->wev_copied[slot], c->cstream));
+    HIPCHK(hipStreamWaitEvent(c->stream, c->wev_copied[slot], 0));
+    TRY(launch_write(c, c->stream, P<uint8_t>(c, (BufId)(B_WPAY0 + slot)), P<uint8_t>(c, (BufId)(B_WKEY0 + slot)),
+                     P<srd_write_entry>(c, (BufId)(B_WENT0 + slot)), e1 - e0, d_out, base, kh_dev + e0, mo_dev + e0));
+    HIPCHK(hipEventRecord(c->wev_done[slot], c->stream));
+    e0 = e1;
+  }
+  if (kh_out) HIPCHK(hipMemcpyAsync(kh_out, kh_dev, n * 8, hipMemcpyDeviceToHost, c->stream));
+  if (mo_out) HIPCHK(hipMemcpyAsync(mo_out, mo_dev, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(spin_sync(c->stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Device KeyIndexer table + batched keyed reads (srd_index.hip)
+static uint32_t table_log2cap(uint64_t table_bytes) {
+  uint32_t l = 0;
+  while (l < 62 && (16ull << (l + 1)) <= table_bytes) l++;
+  return l;
+}
+extern "C" uint64_t srd_index_table_bytes(uint64_t n) {
+  uint64_t cap = 64;
+  while (cap < 2 * n) cap <<= 1;
+  return 16 * cap;
+}
+static unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 8192)); }
+
+extern "C" int srd_index_table_build_device(srd_ctx* c, const uint64_t* d_keys, const uint64_t* d_packed, uint64_t n,
+                                            void* d_table, uint64_t table_bytes) {
+  if (!c || !d_table || (n && (!d_keys || !d_packed)) || table_bytes < srd_index_table_bytes(n)) {
+    set_err("bad argument (table_bytes < srd_index_table_bytes(n)?)");
+    return SRD_ERR_ARG;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  const uint32_t l = table_log2cap(table_bytes);
+  uint64_t* tk = (uint64_t*)d_table;
+  uint64_t* tp = tk + (1ull << l);
+  HIPCHK(hipMemsetAsync(tp, 0xFF, (1ull << l) * 8, c->stream));
+  if (n) {
+    idx_table_insert_kernel<<<grid_for(n), 256, 0, c->stream>>>(d_keys, d_packed, n, tk, (unsigned long long*)tp, l);
+    KCHK(c, "idx_table_insert_kernel");
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(spin_sync(c->stream));
+  return 0;
+}
+
+extern "C" int srd_index_get_packed_device(srd_ctx* c, const void* d_table, uint64_t table_bytes,
+                                           const uint64_t* d_hashes, uint64_t n, uint64_t* d_packed_out,
+                                           void* stream) {
+  if (!c || !d_table || table_bytes < 16 * 64 || (n && (!d_hashes || !d_packed_out))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  if (!n) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  const uint32_t l = table_log2cap(table_bytes);
+  const uint64_t* tk = (const uint64_t*)d_table;
+  idx_get_packed_kernel<<<grid_for(n), 256, 0, stream ? (hipStream_t)stream : c->stream>>>(tk, tk + (1ull << l), l,
+                                                                                             d_hashes, n, d_packed_out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int srd_batch_read_hashed_device(srd_ctx* c, const void* d_table, uint64_t table_bytes,
+                                            const uint8_t* d_file, uint64_t flen, const uint64_t* d_hashes,
+                                            const uint64_t* d_verify, uint64_t n, uint64_t* d_start, uint64_t* d_end,
+                                            void* stream) {
+  if (!c || !d_table || table_bytes < 16 * 64 || (n && (!d_hashes || !d_start || !d_end || (flen && !d_file)))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  if (!n) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  const uint32_t l = table_log2cap(table_bytes);
+  const uint64_t* tk = (const uint64_t*)d_table;
+  batch_read_kernel<<<grid_for(n), 256, 0, stream ? (hipStream_t)stream : c->stream>>>(
+      tk, tk + (1ull << l), l, d_file, flen, d_hashes, d_verify, n, d_start, d_end);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int srd_batch_read(srd_ctx* c, const void* d_table, uint64_t table_bytes, const uint8_t* d_file,
+                              uint64_t flen, const uint8_t* keys, const uint64_t* key_offs, const uint64_t* key_lens,
+                              uint64_t n, uint64_t* start_out, uint64_t* end_out) {
+  if (!c || (n && (!keys || !key_offs || !key_lens || !start_out || !end_out))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  if (!n) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  uint64_t klen = 0;
+  for (uint64_t i = 0; i < n; i++) klen = std::max(klen, key_offs[i] + key_lens[i]);
+  void *dk = nullptr, *dof = nullptr, *dl = nullptr, *dh = nullptr, *ds = nullptr, *de = nullptr;
+  int r = 0;
+  auto cleanup = [&] { hipFree(dk); hipFree(dof); hipFree(dl); hipFree(dh); hipFree(ds); hipFree(de); };
+  if (hipMalloc(&dk, klen + 1) || hipMalloc(&dof, n * 8) || hipMalloc(&dl, n * 8) || hipMalloc(&dh, n * 8) ||
+      hipMalloc(&ds, n * 8) || hipMalloc(&de, n * 8)) {
+    cleanup();
+    set_err("hipMalloc failed");
+    return SRD_ERR_ALLOC;
+  }
+  if (klen) HIPCHK(hipMemcpyAsync(dk, keys, klen, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dof, key_offs, n * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dl, key_lens, n * 8, hipMemcpyHostToDevice, c->stream));
+  r = srd_xxh3_64_batch_device(c, (const uint8_t*)dk, (const uint64_t*)dof, (const uint64_t*)dl, n, (uint64_t*)dh,
+                               nullptr);  // compute_hash_batch (data_store.rs:1112)
+  // batch_read verifies every key by its own tag (Some(keys), :1113)
+  if (!r) r = srd_batch_read_hashed_device(c, d_table, table_bytes, d_file, flen, (const uint64_t*)dh,
+                                           (const uint64_t*)dh, n, (uint64_t*)ds, (uint64_t*)de, nullptr);
+  if (!r) {
+    HIPCHK(hipMemcpyAsync(start_out, ds, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(end_out, de, n * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(spin_sync(c->stream));
+  cleanup();
+  return r;
+}
+
+// ---------------------------------------------------------------------------
+// par_iter_entries / EntryIterator, estimate_compaction_savings and compact
+// over the device index (srd_index.hip iter_* kernels + the writer)
+static int iter_run(Ctx* c, const uint8_t* d_file, uint64_t flen, const uint64_t* d_packed, uint64_t n,
+                    uint64_t* d_start, uint64_t* d_end, uint64_t* d_meta, uint64_t* d_kh, uint64_t* n_out,
+                    uint64_t* kept_bytes) {
+  *n_out = 0;
+  if (kept_bytes) *kept_bytes = 0;
+  if (!n) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  TRY(ensure(c, B_IT_FLAG, n * 4));
+  TRY(ensure(c, B_IT_POS, n * 4));
+  TRY(ensure(c, B_IT_ST, n * 8));
+  TRY(ensure(c, B_IT_EN, n * 8));
+  TRY(ensure(c, B_IT_KEPT, 64));
+  TRY(ensure_cub(c, n));
+  uint32_t* flag = P<uint32_t>(c, B_IT_FLAG);
+  uint32_t* pos = P<uint32_t>(c, B_IT_POS);
+  unsigned long long* kept = P<unsigned long long>(c, B_IT_KEPT);
+  HIPCHK(hipMemsetAsync(kept, 0, 8, c->stream));
+  iter_flag_kernel<<<grid_for(n), 256, 0, c->stream>>>(d_file, flen, d_packed, n, flag, P<uint64_t>(c, B_IT_ST),
+                                                       P<uint64_t>(c, B_IT_EN), kept);
+  KCHK(c, "iter_flag_kernel");
+  TRY(scan_sum(c, flag, pos, n));
+  uint32_t last[2] = {0, 0};
+  unsigned long long hk = 0;
+  HIPCHK(hipMemcpyAsync(&last[0], pos + n - 1, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&last[1], flag + n - 1, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&hk, kept, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(spin_sync(c->stream));
+  const uint64_t nv = (uint64_t)last[0] + last[1];
+  if (d_start && nv) {
+    iter_emit_kernel<<<grid_for(n), 256, 0, c->stream>>>(d_file, d_packed, flag, pos, n, nv, P<uint64_t>(c, B_IT_ST),
+                                                         P<uint64_t>(c, B_IT_EN), d_start, d_end, d_meta, d_kh);
+    KCHK(c, "iter_emit_kernel");
+    HIPCHK(hipGetLastError());
+    HIPCHK(spin_sync(c->stream));
+  }
+  *n_out = nv;
+  if (kept_bytes) *kept_bytes = hk;
+  return 0;
+}
+
+extern "C" int srd_iter_entries_device(srd_ctx* c, const uint8_t* d_file, uint64_t flen, const uint64_t* d_packed,
+                                       uint64_t n_index, uint64_t* d_start, uint64_t* d_end, uint64_t* d_meta_off,
+                                       uint64_t* d_key_hash, uint64_t* n_out) {
+  if (!c || !n_out || (n_index && (!d_file || !d_packed || !d_start || !d_end))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  return iter_run(c, d_file, flen, d_packed, n_index, d_start, d_end, d_meta_off, d_key_hash, n_out, nullptr);
+}
+
+extern "C" int srd_estimate_compaction_savings_device(srd_ctx* c, const uint8_t* d_file, uint64_t flen,
+                                                      const uint64_t* d_packed, uint64_t n_index, uint64_t* savings) {
+  if (!c || !savings || (n_index && (!d_file || !d_packed))) { set_err("bad argument"); return SRD_ERR_ARG; }
+  uint64_t nv = 0, kept = 0;
+  TRY(iter_run(c, d_file, flen, d_packed, n_index, nullptr, nullptr, nullptr, nullptr, &nv, &kept));
+  *savings = flen > kept ? flen - kept : 0;  // total_size.saturating_sub(unique_entry_size)
+  return 0;
+}
+
+extern "C" int srd_compact_device(srd_ctx* c, const uint8_t* d_file, uint64_t flen, const uint64_t* d_packed,
+                                  uint64_t n_index, uint8_t* d_out, uint64_t out_cap, uint64_t* new_len,
+                                  uint64_t* d_key_hash_out, uint64_t* d_meta_off_out) {
+  if (!c || !new_len || (n_index && (!d_file || !d_packed))) { set_err("bad argument"); return SRD_ERR_ARG; }
+  *new_len = 0;
+  if (!n_index) return 0;
+  TRY(ensure(c, B_IT_OST, n_index * 8));
+  TRY(ensure(c, B_IT_OEN, n_index * 8));
+  TRY(ensure(c, B_IT_OKH, n_index * 8));
+  uint64_t nv = 0;
+  TRY(iter_run(c, d_file, flen, d_packed, n_index, P<uint64_t>(c, B_IT_OST), P<uint64_t>(c, B_IT_OEN), nullptr,
+               P<uint64_t>(c, B_IT_OKH), &nv, nullptr));
+  // layout of the compacted file on the device: write_stream_with_key_hash
+  // per entry in iter_entries order (data_store.rs:706-719, 758-825), tail
+  // from 0 -- a prefix sum (compact_sizes_kernel), then the write entries
+  if (!nv) return 0;
+  const uint64_t* st = P<uint64_t>(c, B_IT_OST);
+  const uint64_t* en = P<uint64_t>(c, B_IT_OEN);
+  TRY(ensure(c, B_IT_RLEN, nv * 8));
+  TRY(ensure(c, B_IT_PST, nv * 8));
+  TRY(ensure(c, B_IT_ENT, nv * sizeof(srd_write_entry)));
+  TRY(ensure(c, B_IT_KEPT, 64));
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)nv));
+  KCHK(c, "hipcub");
+  TRY(ensure(c, B_CUB_TMP, tb + 256));
+  compact_sizes_kernel<<<grid_for(nv), 256, 0, c->stream>>>(st, en, nv, P<uint64_t>(c, B_IT_RLEN));
+  KCHK(c, "compact_sizes_kernel");
+  TRY(scan_sum(c, P<uint64_t>(c, B_IT_RLEN), P<uint64_t>(c, B_IT_PST), nv));
+  uint64_t* d_new_len = P<uint64_t>(c, B_IT_KEPT) + 2;
+  compact_entries_kernel<<<grid_for(nv), 256, 0, c->stream>>>(st, en, P<uint64_t>(c, B_IT_OKH), P<uint64_t>(c, B_IT_PST),
+                                                             nv, P<srd_write_entry>(c, B_IT_ENT), d_new_len);
+  KCHK(c, "compact_entries_kernel");
+  HIPCHK(hipGetLastError());
+  uint64_t tail = 0;
+  HIPCHK(hipMemcpyAsync(&tail, d_new_len, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(spin_sync(c->stream));
+  *new_len = tail;
+  if (!d_out) return 0;
+  if (tail > out_cap) { set_err("out_cap too small for the compacted store"); return SRD_ERR_ARG; }
+  TRY(ensure(c, B_WKH, nv * 8));
+  TRY(ensure(c, B_WMO, nv * 8));
+  unsigned int* nullf = (unsigned int*)(P<uint8_t>(c, B_IT_KEPT) + 8);
+  HIPCHK(hipMemsetAsync(nullf, 0, 4, c->stream));
+  TRY(launch_write(c, c->stream, d_file, nullptr, P<srd_write_entry>(c, B_IT_ENT), nv, d_out, 0,
+                   d_key_hash_out ? d_key_hash_out : P<uint64_t>(c, B_WKH),
+                   d_meta_off_out ? d_meta_off_out : P<uint64_t>(c, B_WMO), nullf));
+  unsigned int hn = 0;
+  HIPCHK(hipMemcpyAsync(&hn, nullf, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(spin_sync(c->stream));
+  if (hn) {  // write_stream rejects NULL-only payloads (data_store.rs:792-797); compact() fails with it
+    set_err("NULL-byte-only streams cannot be written directly.");
+    return SRD_ERR_ARG;
+  }
+  return 0;
+}
