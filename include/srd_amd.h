@@ -460,6 +460,73 @@ int srd_batch_read(srd_ctx *ctx, const void *d_table, uint64_t table_bytes,
                    const uint64_t *key_offs, const uint64_t *key_lens, uint64_t n,
                    uint64_t *start_out, uint64_t *end_out);
 
+/* ---- the device KeyIndexer kept live: appends and deletes in place ----
+ *   srd_index_table_apply_device   <- DataStore::reindex (data_store.rs:224-259)
+ *                                     over KeyIndexer::insert (key_indexer.rs:135-160)
+ *                                     and KeyIndexer::remove (:174-178), the
+ *                                     step every write ends in (:936)
+ *   srd_index_table_export_device  <- the live map's pairs in file order (what
+ *                                     KeyIndexer::build would give without the
+ *                                     removed keys), for the iterator /
+ *                                     compaction calls below and for growth
+ *   srd_batch_delete_hashed_device <- DataStoreWriter::batch_delete_key_hashes
+ *                                     (data_store.rs:995-1024)
+ * The table is the one srd_index_table_build_device fills.  A removed key's
+ * slot keeps its key and holds the value ~0 - 1 ("deleted": no packed value,
+ * its offset 2^48 - 2 lies above any file_len); every read reports such a key
+ * as absent (SRD_INDEX_NONE / start == end == 0) and probes on past it, and a
+ * later insert of the key revives the slot.  `used` counts the slots that
+ * are not empty (live + deleted): n after a build; it only grows, and a table
+ * holds at most capacity / 2 of them (capacity = the largest power of two
+ * with 16 * capacity <= table_bytes).  To grow, or to drop the deleted slots:
+ * export, then srd_index_table_build_device into a larger buffer.
+ * A table that is built and never modified answers exactly as before. */
+#define SRD_ERR_FULL (-5) /* the batch's new keys would push the used slots above capacity / 2; table unchanged */
+typedef struct {
+  uint64_t n_inserted; /* distinct keys absent before, present after */
+  uint64_t n_updated;  /* present before and after */
+  uint64_t n_removed;  /* present before, absent after */
+} srd_index_apply_stats;
+/* The reference's loop over n (key_hash, metadata offset) device pairs in
+ * batch order -- d_kh_out / d_mo_out of srd_batch_write_device as they are;
+ * d_tomb (nullable) marks the pairs that are tombstones.  Afterwards every
+ * key with at least one tombstone pair in the batch is absent (deleted_keys,
+ * data_store.rs:861,896: also when the batch wrote it, before or after), and
+ * every other key maps to pack(key_hash >> 48, offset) of its last pair.
+ * SRD_ERR_FULL: *used + the batch's distinct new keys > capacity / 2; nothing
+ * was written (the look-up runs first, the commit second).
+ * Ordered on `stream`; waits once, for the look-up's counts, and returns
+ * with the commit enqueued: later work on `stream` sees the new table. */
+int srd_index_table_apply_device(srd_ctx *ctx, void *d_table,
+                                 uint64_t table_bytes, uint64_t *used,
+                                 const uint64_t *d_key_hashes,
+                                 const uint64_t *d_meta_offs,
+                                 const uint8_t *d_tomb, uint64_t n,
+                                 srd_index_apply_stats *stats, void *stream);
+/* The live (key_hash, packed) pairs in ascending metadata offset (file order,
+ * the order of srd_device_result's index arrays) into device arrays of
+ * cap_out elements; *n_live = their number.  Both outputs NULL: the count
+ * only.  On the context stream; synchronises. */
+int srd_index_table_export_device(srd_ctx *ctx, const void *d_table,
+                                  uint64_t table_bytes, uint64_t *d_keys_out,
+                                  uint64_t *d_packed_out, uint64_t cap_out,
+                                  uint64_t *n_live);
+/* Keeps the hashes the index holds (input order, duplicates kept; a removed
+ * key is absent, a key whose indexed entry is a tombstone on disk is held),
+ * appends one tombstone entry per kept hash at `tail` of the store at d_file
+ * (d_file[j] = file byte j, writable to file_cap bytes; 21 bytes each: a NULL
+ * byte, no prepad, prev_offset = the previous tail, CRC 0xD202EF8D) and
+ * removes the keys from the table.  *n_deleted (nullable) = tombstones
+ * written.  Nothing kept: nothing written, *new_tail = tail.  SRD_ERR_ARG
+ * when srd_padded_size(new tail) > file_cap (nothing written).  On the
+ * context stream; synchronises. */
+int srd_batch_delete_hashed_device(srd_ctx *ctx, void *d_table,
+                                   uint64_t table_bytes, uint64_t *used,
+                                   const uint64_t *d_hashes, uint64_t n,
+                                   uint64_t tail, uint8_t *d_file,
+                                   uint64_t file_cap, uint64_t *new_tail,
+                                   uint64_t *n_deleted);
+
 /* ---- iteration and compaction over the device index ----
  *   srd_iter_entries_device   <- EntryIterator (entry_iterator.rs:69-126) /
  *                                par_iter_entries (data_store.rs:297-361):

@@ -9,6 +9,7 @@
 //     srd_glue.hip            sync-free glue of the optimistic pass, bucketed index, owner partition
 //     srd_writer.hip          batch writer
 //     srd_index.hip           lookup table, batched reads, iterator, compaction
+//     srd_index_live.hip      the table kept live: apply, export, batched delete
 //     srd_probe.hip           stream probe
 //   host code (in include order: each file uses only the ones above it)
 //     srd_host.cpp / .h       no-HIP parsers (shard cuts, batch layout)
@@ -18,7 +19,8 @@
 //     srd_validate.hip        optimistic pass, full pass, finish; the two validate entries
 //     srd_host_input.hip      staging, pinned host results, host-pointer entries
 //     srd_multi.hip           multi-GPU open
-//     srd_ops.hip             probe, batch digests, synth, writer, table / reads, iterator, compaction
+//     srd_ops.hip             probe, batch digests, synth, writer, table / reads / maintenance, iterator,
+//                             compaction
 //   this file               error / build-info entries, stamps read-outs, host self-test
 //
 // Glue scans/compactions use hipCUB (library primitives, like calling
@@ -47,6 +49,7 @@
 #include "srd_glue.hip"
 #include "srd_writer.hip"
 #include "srd_index.hip"
+#include "srd_index_live.hip"
 #include "srd_probe.hip"
 
 using namespace srd;

@@ -218,6 +218,8 @@ enum BufId {
   B_GKEY, B_GVAL, B_GOKEY, B_GOPACKED,
   B_WTOT, B_WROOT, B_KTOT, B_DONE, B_SPAN_FIRST,
   B_XKEY, B_XVAL, B_GATHER, B_RFLAG, B_O_PACKED, B_VSCAN, B_LOOKB, B_PROBE, B_XTOT,
+  B_LV_DSLOT, B_LV_DTOMB, B_LV_LSLOT, B_LV_OPS, B_LV_OPV, B_LV_CNT,  // live table: apply
+  B_LV_XK, B_LV_XP, B_LV_FLAG, B_LV_POS, B_LV_ENT, B_LV_TOMB,        // export, batched delete
   B_COUNT_
 };
 

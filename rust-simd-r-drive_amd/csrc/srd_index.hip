@@ -11,10 +11,15 @@
 // (two u64 arrays); an empty slot holds packed == ~0 (a packed value is
 // tag16 << 48 | offset48 with offset < file_len, never all ones).  Keys are
 // unique (an index), so an insert only claims a slot: CAS on packed.
+// A table kept live (srd_index_live.hip) also holds removed keys: their slots
+// keep the key and hold TBL_DELETED, which reads as absent and does not end a
+// probe (~0 - 1 is no packed value either: tag 0xFFFF with offset 2^48 - 2,
+// and an offset lies below file_len).
 
 namespace srd {
 
 constexpr uint64_t TBL_EMPTY = ~0ull;
+constexpr uint64_t TBL_DELETED = ~0ull - 1;
 
 __device__ __forceinline__ uint64_t idx_slot(uint64_t k, uint32_t log2cap) {
   k ^= k >> 29;  // key hashes are XXH3 outputs already; one mix keeps clustered inputs spread
@@ -44,7 +49,7 @@ __device__ __forceinline__ uint64_t idx_get_packed(const uint64_t* tkeys, const 
   for (;;) {
     const uint64_t p = tpacked[s];
     if (p == TBL_EMPTY) return TBL_EMPTY;
-    if (tkeys[s] == k) return p;
+    if (tkeys[s] == k) return p == TBL_DELETED ? TBL_EMPTY : p;
     s = (s + 1) & mask;
   }
 }

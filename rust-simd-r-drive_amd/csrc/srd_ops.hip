@@ -1,6 +1,7 @@
 // srd_ops.hip -- host launch code of the remaining kernel families (included
 // by srd_api.hip): stream probe, batch digests, synth, batch writer, device
-// lookup table and batched reads, iterator and compaction.
+// lookup table, batched reads and the table's maintenance, iterator and
+// compaction.
 extern "C" int srd_stream_probe_device(srd_ctx* c, const uint8_t* d_buf, uint64_t bytes, int reps, double* best_ms,
                                        double* median_ms) {
   if (!c || !d_buf || bytes < TILE || reps < 1 || !best_ms) { set_err("bad argument"); return SRD_ERR_ARG; }
@@ -389,6 +390,177 @@ extern "C" int srd_batch_read(srd_ctx* c, const void* d_table, uint64_t table_by
   HIPCHK(spin_sync(c->stream));
   cleanup();
   return r;
+}
+
+// ---------------------------------------------------------------------------
+// The table kept live (srd_index_live.hip): reindex, export, batched delete
+static bool table_ok(const void* d_table, uint64_t table_bytes) { return d_table && table_bytes >= 16 * 64; }
+
+// reindex (data_store.rs:224-259) of n pairs on stream s: dedupe and look up
+// (the table is only read), one host wait for the counts, then the commit.
+// SRD_ERR_FULL leaves the table as it was: nothing has written it yet.
+static int apply_impl(Ctx* c, void* d_table, uint64_t table_bytes, uint64_t* used, const uint64_t* kh,
+                      const uint64_t* mo, const uint8_t* tomb, uint64_t n, srd_index_apply_stats* stats,
+                      hipStream_t s) {
+  if (stats) *stats = srd_index_apply_stats{0, 0, 0};
+  if (!n) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  uint32_t log2dc = 6;
+  while ((1ull << log2dc) < 2 * n) log2dc++;
+  const uint64_t dc = 1ull << log2dc;
+  TRY(ensure(c, B_LV_DSLOT, dc * 4));
+  TRY(ensure(c, B_LV_DTOMB, dc / 32 * 4));
+  TRY(ensure(c, B_LV_LSLOT, n * 4));
+  TRY(ensure(c, B_LV_OPS, n * 8));
+  TRY(ensure(c, B_LV_OPV, n * 8));
+  TRY(ensure(c, B_LV_CNT, 64));
+  LiveArgs a{};
+  a.kh = kh;
+  a.mo = mo;
+  a.tomb = tomb;
+  a.n = n;
+  a.dslot = P<uint32_t>(c, B_LV_DSLOT);
+  a.dtomb = P<uint32_t>(c, B_LV_DTOMB);
+  a.log2dc = log2dc;
+  a.lslot = P<uint32_t>(c, B_LV_LSLOT);
+  a.log2cap = table_log2cap(table_bytes);
+  a.tkeys = (uint64_t*)d_table;
+  a.tpacked = a.tkeys + (1ull << a.log2cap);
+  a.op_slot = P<uint64_t>(c, B_LV_OPS);
+  a.op_val = P<uint64_t>(c, B_LV_OPV);
+  a.cnt = P<unsigned long long>(c, B_LV_CNT);
+  HIPCHK(hipMemsetAsync(a.dslot, 0, dc * 4, s));
+  HIPCHK(hipMemsetAsync(a.dtomb, 0, dc / 32 * 4, s));
+  HIPCHK(hipMemsetAsync(a.cnt, 0, 32, s));
+  live_dedupe_kernel<<<grid_for(n), 256, 0, s>>>(a);
+  live_lookup_kernel<<<grid_for(n), 256, 0, s>>>(a);
+  HIPCHK(hipGetLastError());
+  uint64_t* h = c->h_small + 16;
+  HIPCHK(hipMemcpyAsync(h, a.cnt, 32, hipMemcpyDeviceToHost, s));
+  HIPCHK(spin_sync(s));
+  const uint64_t ins = h[0], upd = h[1], rem = h[2], fresh = h[3];
+  if (*used + fresh > (1ull << a.log2cap) / 2) {
+    set_err("index table full: " + std::to_string(*used) + " used slots + " + std::to_string(fresh) +
+            " new keys exceed half of " + std::to_string(1ull << a.log2cap));
+    return SRD_ERR_FULL;
+  }
+  if (ins + upd + rem) {
+    live_commit_kernel<<<grid_for(n), 256, 0, s>>>(a);
+    HIPCHK(hipGetLastError());
+  }
+  *used += fresh;
+  if (stats) *stats = srd_index_apply_stats{ins, upd, rem};
+  return 0;
+}
+
+extern "C" int srd_index_table_apply_device(srd_ctx* c, void* d_table, uint64_t table_bytes, uint64_t* used,
+                                            const uint64_t* d_key_hashes, const uint64_t* d_meta_offs,
+                                            const uint8_t* d_tomb, uint64_t n, srd_index_apply_stats* stats,
+                                            void* stream) {
+  if (!c || !table_ok(d_table, table_bytes) || !used || n >= (1ull << 31) || (n && (!d_key_hashes || !d_meta_offs))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  return apply_impl(c, d_table, table_bytes, used, d_key_hashes, d_meta_offs, d_tomb, n, stats,
+                    stream ? (hipStream_t)stream : c->stream);
+}
+
+extern "C" int srd_index_table_export_device(srd_ctx* c, const void* d_table, uint64_t table_bytes,
+                                             uint64_t* d_keys_out, uint64_t* d_packed_out, uint64_t cap_out,
+                                             uint64_t* n_live) {
+  if (!c || !table_ok(d_table, table_bytes) || !n_live || (!d_keys_out != !d_packed_out)) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  const uint32_t l = table_log2cap(table_bytes);
+  const uint64_t cap = 1ull << l;
+  const uint64_t* tk = (const uint64_t*)d_table;
+  TRY(ensure(c, B_LV_CNT, 64));
+  unsigned long long* cnt = P<unsigned long long>(c, B_LV_CNT) + 4;
+  uint64_t* h = c->h_small + 16;
+  HIPCHK(hipMemsetAsync(cnt, 0, 8, c->stream));
+  live_count_kernel<<<grid_for(cap), 256, 0, c->stream>>>(tk + cap, cap, cnt);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h, cnt, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(spin_sync(c->stream));
+  const uint64_t nl = h[0];
+  *n_live = nl;
+  if (!d_keys_out || !nl) return 0;
+  if (nl > cap_out) { set_err("cap_out too small for the live pairs"); return SRD_ERR_ARG; }
+  if (nl >= (1ull << 31)) { set_err("too many pairs"); return SRD_ERR_ARG; }
+  // file order = ascending metadata offset: the offsets are distinct, so a
+  // radix sort over the 48 offset bits of the packed words fixes the order
+  // whatever order the gather's atomic counter handed out
+  TRY(ensure(c, B_LV_XK, nl * 8));
+  TRY(ensure(c, B_LV_XP, nl * 8));
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                            (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)nl, 0, 48, c->stream));
+  TRY(ensure(c, B_CUB_TMP, tb + 256));
+  HIPCHK(hipMemsetAsync(cnt, 0, 8, c->stream));
+  live_gather_kernel<<<grid_for(cap), 256, 0, c->stream>>>(tk, tk + cap, cap, cnt, P<uint64_t>(c, B_LV_XK),
+                                                          P<uint64_t>(c, B_LV_XP), nl);
+  KCHK(c, "live_gather_kernel");
+  tb = c->bufs[B_CUB_TMP].n;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(P<void>(c, B_CUB_TMP), tb, (const uint64_t*)P<uint64_t>(c, B_LV_XP),
+                                            d_packed_out, (const uint64_t*)P<uint64_t>(c, B_LV_XK), d_keys_out,
+                                            (int)nl, 0, 48, c->stream));
+  KCHK(c, "hipcub");
+  HIPCHK(hipGetLastError());
+  HIPCHK(spin_sync(c->stream));
+  return 0;
+}
+
+extern "C" int srd_batch_delete_hashed_device(srd_ctx* c, void* d_table, uint64_t table_bytes, uint64_t* used,
+                                              const uint64_t* d_hashes, uint64_t n, uint64_t tail, uint8_t* d_file,
+                                              uint64_t file_cap, uint64_t* new_tail, uint64_t* n_deleted) {
+  if (!c || !table_ok(d_table, table_bytes) || !used || !new_tail || n >= (1ull << 31) ||
+      (n && (!d_hashes || !d_file))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  *new_tail = tail;
+  if (n_deleted) *n_deleted = 0;
+  if (!n) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  const uint32_t l = table_log2cap(table_bytes);
+  const uint64_t* tk = (const uint64_t*)d_table;
+  TRY(ensure(c, B_LV_FLAG, n * 4));
+  TRY(ensure(c, B_LV_POS, n * 4));
+  TRY(ensure_cub(c, n));
+  uint32_t* flag = P<uint32_t>(c, B_LV_FLAG);
+  uint32_t* pos = P<uint32_t>(c, B_LV_POS);
+  live_present_kernel<<<grid_for(n), 256, 0, c->stream>>>(tk, tk + (1ull << l), l, d_hashes, n, flag);
+  KCHK(c, "live_present_kernel");
+  TRY(scan_sum(c, flag, pos, n));
+  uint32_t* h = (uint32_t*)(c->h_small + 20);
+  HIPCHK(hipMemcpyAsync(h, pos + n - 1, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(h + 1, flag + n - 1, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(spin_sync(c->stream));
+  const uint64_t nk = (uint64_t)h[0] + h[1];
+  if (!nk) return 0;  // (the reference returns the unchanged tail: data_store.rs:1011-1014)
+  const uint64_t nt = tail + 21 * nk;
+  if (srd_padded_size(nt) > file_cap) { set_err("file_cap too small for the tombstones"); return SRD_ERR_ARG; }
+  TRY(ensure(c, B_LV_ENT, nk * sizeof(srd_write_entry)));
+  TRY(ensure(c, B_LV_TOMB, nk));
+  TRY(ensure(c, B_WKH, nk * 8));
+  TRY(ensure(c, B_WMO, nk * 8));
+  live_tomb_entries_kernel<<<grid_for(n), 256, 0, c->stream>>>(d_hashes, flag, pos, n, tail,
+                                                              P<srd_write_entry>(c, B_LV_ENT));
+  KCHK(c, "live_tomb_entries_kernel");
+  HIPCHK(hipMemsetAsync(P<void>(c, B_LV_TOMB), 1, nk, c->stream));
+  // (a tombstone reads no payload or key bytes: d_file only stands for the payload base)
+  TRY(launch_write(c, c->stream, d_file, nullptr, P<srd_write_entry>(c, B_LV_ENT), nk, d_file, 0,
+                   P<uint64_t>(c, B_WKH), P<uint64_t>(c, B_WMO)));
+  // every kept key was present and every pair is a tombstone: the apply
+  // removes them all and needs no new slot, so it cannot be refused
+  TRY(apply_impl(c, d_table, table_bytes, used, P<uint64_t>(c, B_WKH), P<uint64_t>(c, B_WMO), P<uint8_t>(c, B_LV_TOMB),
+                 nk, nullptr, c->stream));
+  HIPCHK(spin_sync(c->stream));
+  *new_tail = nt;
+  if (n_deleted) *n_deleted = nk;
+  return 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -40,6 +40,7 @@ SRD_MODE_SPAN_UNPROVEN = 3
 # srd_device_result.full_reason (include/srd_amd.h)
 SRD_FULL_NONE, SRD_FULL_FORCED, SRD_FULL_SLOT_SPACE, SRD_FULL_WAVES = 0, 1, 2, 3
 SRD_FULL_NO_START, SRD_FULL_UNPROVEN, SRD_FULL_CAP, SRD_FULL_LOOKBACK = 4, 5, 6, 7
+SRD_ERR_ARG, SRD_ERR_FULL = -3, -5
 SRD_FLAG_MERGE_INDEX = 16  # multi-GPU open: the whole index on ctxs[0] (default: by owner)
 SRD_MULTI_COMPOSED, SRD_MULTI_NEIGHBOUR, SRD_MULTI_WHOLE_FILE = 0, 1, 2  # srd_multi_summary.path
 SPAN_ALIGN = 16384  # span_off granularity of srd_validate_span_device
@@ -67,6 +68,7 @@ EXPORTS = [
     "srd_shard_cuts", "srd_validate_index_multi", "srd_ctx_stage_info", "srd_index_hash_device",
     "srd_validate_index_multi_device", "srd_ctx_multi_summary", "srd_ctx_scan_list", "srd_ctx_set_timing_every",
     "srd_stream_probe_device", "srd_ctx_multi_shard_ms",
+    "srd_index_table_apply_device", "srd_index_table_export_device", "srd_batch_delete_hashed_device",
 ]
 
 
@@ -92,6 +94,14 @@ class MultiSummary(C.Structure):
         ("validate_ms", C.c_double), ("exchange_ms", C.c_double), ("total_ms", C.c_double),
         ("index_key_hash", C.c_void_p), ("index_packed", C.c_void_p),
     ]
+
+
+class ApplyStats(C.Structure):
+    """srd_index_apply_stats (include/srd_amd.h): per distinct key of the batch"""
+    _fields_ = [("n_inserted", C.c_uint64), ("n_updated", C.c_uint64), ("n_removed", C.c_uint64)]
+
+    def as_tuple(self):
+        return int(self.n_inserted), int(self.n_updated), int(self.n_removed)
 
 
 def build_info() -> str:
@@ -173,6 +183,11 @@ def lib():
         L.srd_index_get_packed_device.argtypes = [vp, vp, u64, vp, u64, vp, vp]
         L.srd_batch_read_hashed_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp]
         L.srd_batch_read.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, vp, vp]
+        L.srd_index_table_apply_device.argtypes = [vp, vp, u64, C.POINTER(u64), vp, vp, vp, u64,
+                                                   C.POINTER(ApplyStats), vp]
+        L.srd_index_table_export_device.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
+        L.srd_batch_delete_hashed_device.argtypes = [vp, vp, u64, C.POINTER(u64), vp, u64, u64, vp, u64,
+                                                     C.POINTER(u64), C.POINTER(u64)]
         L.srd_iter_entries_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
         L.srd_estimate_compaction_savings_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.srd_compact_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, vp]
@@ -822,6 +837,113 @@ class DeviceIndex:
         self.table = torch.empty(self.nbytes, dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
         _check(lib().srd_index_table_build_device(self.ctx.h, C.c_void_p(d_keys), C.c_void_p(d_packed), n,
                                                   C.c_void_p(self.table.data_ptr()), self.nbytes))
+        self._used = n      # slots that are not empty (live + deleted)
+        self._live = n      # KeyIndexer::len; None = count on demand (after a delete through the C call)
+
+    # -- kept live: reindex (data_store.rs:224-259) on the table in place -----------------
+
+    def _lib_after_torch(self):
+        """The context stream waits for what torch's current stream holds (inputs
+        torch wrote): an event, no host wait."""
+        import torch
+        dev = self.table.device
+        torch.cuda.ExternalStream(self.ctx.stream, device=dev).wait_stream(torch.cuda.current_stream(dev))
+
+    def _sync_lib(self):
+        """The host waits for the context stream (before torch reads what the library wrote)."""
+        import torch
+        torch.cuda.ExternalStream(self.ctx.stream, device=self.table.device).synchronize()
+
+    def _as_dev(self, a, dtype=np.uint64):
+        import torch
+        if isinstance(a, torch.Tensor):
+            return a.to(self.table.device).contiguous()
+        h = np.ascontiguousarray(a, dtype)
+        return torch.from_numpy(h.view(np.int64) if dtype == np.uint64 else h).to(self.table.device)
+
+    @property
+    def used(self) -> int:
+        """Slots that are not empty: live keys plus removed ones (at most capacity / 2)."""
+        return self._used
+
+    @property
+    def capacity(self) -> int:
+        return 1 << ((self.nbytes // 16).bit_length() - 1)
+
+    def __len__(self) -> int:
+        """KeyIndexer::len: the live keys."""
+        if self._live is None:
+            n = C.c_uint64()
+            self._lib_after_torch()
+            _check(lib().srd_index_table_export_device(self.ctx.h, C.c_void_p(self.table.data_ptr()), self.nbytes,
+                                                       None, None, 0, C.byref(n)))
+            self._live = int(n.value)
+        return self._live
+
+    def export(self):
+        """The live (key_hash, packed) pairs in file order (ascending metadata
+        offset) as two device int64 tensors -- the index arrays the iterator and
+        compaction calls take."""
+        import torch
+        n = len(self) if self._live is not None else self._used
+        k = torch.empty(max(n, 1), dtype=torch.int64, device=self.table.device)
+        p = torch.empty_like(k)
+        got = C.c_uint64()
+        self._lib_after_torch()
+        _check(lib().srd_index_table_export_device(self.ctx.h, C.c_void_p(self.table.data_ptr()), self.nbytes,
+                                                   C.c_void_p(k.data_ptr()), C.c_void_p(p.data_ptr()), k.numel(),
+                                                   C.byref(got)))  # synchronises
+        self._live = int(got.value)
+        return k[: self._live], p[: self._live]
+
+    def grow(self, n_keys: int):
+        """A table for at least n_keys keys: export, then build into a larger
+        buffer (which also drops the removed keys' slots)."""
+        import torch
+        k, p = self.export()
+        n = k.numel()
+        nbytes = int(lib().srd_index_table_bytes(max(n_keys, n)))
+        table = torch.empty(nbytes, dtype=torch.uint8, device=self.table.device)
+        self._lib_after_torch()
+        _check(lib().srd_index_table_build_device(self.ctx.h, C.c_void_p(k.data_ptr()), C.c_void_p(p.data_ptr()), n,
+                                                  C.c_void_p(table.data_ptr()), nbytes))  # synchronises
+        self.table, self.nbytes, self.n, self._used, self._live = table, nbytes, n, n, n
+
+    def apply(self, key_hashes, meta_offs, tomb=None) -> tuple[int, int, int]:
+        """DataStore::reindex of a batch of (key_hash, metadata offset[, tombstone])
+        pairs -- host arrays or device tensors, e.g. the writer's outputs.  Returns
+        (inserted, updated, removed) per distinct key.  A batch the table has no
+        room for grows it (export + rebuild at twice the need) and is applied then."""
+        kh, mo = self._as_dev(key_hashes), self._as_dev(meta_offs)
+        tb = self._as_dev(tomb, np.uint8) if tomb is not None else None
+        n = kh.numel()
+        if mo.numel() != n or (tb is not None and tb.numel() != n):
+            raise ValueError("Mismatched lengths for key hashes, offsets and tombstone flags.")
+        st = ApplyStats()
+        for attempt in range(2):
+            used = C.c_uint64(self._used)
+            self._lib_after_torch()
+            rc = lib().srd_index_table_apply_device(self.ctx.h, C.c_void_p(self.table.data_ptr()), self.nbytes,
+                                                    C.byref(used), C.c_void_p(kh.data_ptr()), C.c_void_p(mo.data_ptr()),
+                                                    C.c_void_p(tb.data_ptr()) if tb is not None else None, n,
+                                                    C.byref(st), C.c_void_p(self.ctx.stream))
+            if rc == SRD_ERR_FULL and attempt == 0:
+                self.grow(2 * (self._used + n))  # room for every pair being a new key, at load <= 1/4
+                continue
+            _check(rc)
+            break
+        self._sync_lib()  # the inputs may be temporaries: the commit has read them before they are released
+        self._used = int(used.value)
+        if self._live is not None:
+            self._live += int(st.n_inserted) - int(st.n_removed)
+        return st.as_tuple()
+
+    def remove(self, key_hashes) -> int:
+        """KeyIndexer::remove for each hash; returns how many keys were present."""
+        kh = self._as_dev(key_hashes)
+        import torch
+        ones = torch.ones(kh.numel(), dtype=torch.uint8, device=self.table.device)
+        return self.apply(kh, torch.zeros_like(kh), ones)[2]
 
     def _dev_u64(self, a):
         import torch
@@ -909,3 +1031,197 @@ def compact_device(d_file: int, file_len: int, d_index_packed: int, n_index: int
                                     C.c_void_p(out.data_ptr()), out.numel(), C.byref(nl), None, None))
     torch.cuda.synchronize()
     return out[: int(nl.value)]
+
+
+# ---------------------------------------------------------------------------
+# A store resident in HBM with its index kept live: write -> reindex -> read
+# (DataStoreWriter / DataStoreReader of data_store.rs over one device buffer)
+
+class DeviceStore:
+    """A store in a device byte buffer of fixed capacity, its tail, and the
+    DeviceIndex of it, maintained in place by every write and delete -- the
+    in-session loop of the reference (batch_write_with_key_hashes ends in
+    reindex, data_store.rs:936).  Each method is named after the reference
+    method it replaces.  All library work runs on the context stream, ordered
+    after torch's current stream where it reads what torch wrote; the host
+    waits for the context stream before torch reads what the library wrote."""
+
+    def __init__(self, buf, tail: int, index: DeviceIndex, ctx: Context):
+        self.buf, self._tail, self.index, self.ctx = buf, tail, index, ctx
+
+    @classmethod
+    def create(cls, capacity: int, ctx: Context | None = None) -> "DeviceStore":
+        """An empty store that can grow to `capacity` bytes."""
+        import torch
+        ctx = ctx or default_ctx()
+        buf = torch.zeros(padded_size(capacity), dtype=torch.uint8, device=f"cuda:{ctx.device}")
+        return cls(buf, 0, DeviceIndex(0, 0, 0, ctx), ctx)
+
+    @classmethod
+    def open(cls, dev_tensor, file_len: int, ctx: Context | None = None) -> "DeviceStore":
+        """DataStore::open (data_store.rs:84-117) of the store in dev_tensor[:file_len]
+        (a uint8 device tensor of at least padded_size(file_len) bytes; its size is
+        the capacity): validates it, adopts the index, and appends at the recovered tail."""
+        import torch
+        ctx = ctx or default_ctx()
+        if dev_tensor.numel() < padded_size(file_len):
+            raise ValueError("the store buffer must hold padded_size(file_len) bytes")
+        torch.cuda.ExternalStream(ctx.stream, device=dev_tensor.device).wait_stream(
+            torch.cuda.current_stream(dev_tensor.device))
+        r = validate_index_device(dev_tensor.data_ptr(), file_len, 0, ctx)  # synchronises
+        return cls(dev_tensor, int(r.final_len), DeviceIndex(r.index_key_hash, r.index_packed, int(r.n_index), ctx), ctx)
+
+    @property
+    def tail(self) -> int:
+        return self._tail
+
+    def len(self) -> int:
+        """DataStoreReader::len (data_store.rs:1164): the index's live keys."""
+        return len(self.index)
+
+    __len__ = len
+
+    def bytes(self) -> bytes:
+        """The store's bytes [0, tail)."""
+        self.index._sync_lib()
+        return self.buf[: self._tail].cpu().numpy().tobytes()
+
+    # -- writes ---------------------------------------------------------------------------
+
+    def batch_write(self, keys, payloads) -> int:
+        """DataStoreWriter::batch_write (data_store.rs:838-843): compute_hash_batch,
+        then batch_write_with_key_hashes."""
+        if len(keys) != len(payloads):
+            raise ValueError("Mismatched lengths for keys and payloads.")
+        return self.batch_write_with_key_hashes(compute_hash_batch(keys, self.ctx), payloads, False)
+
+    def batch_write_with_key_hashes(self, hashes, payloads, allow_null: bool = False) -> int:
+        """data_store.rs:847-939: the entries serialized at the tail by the writer
+        kernel, straight into the store buffer, then the reindex of their (key_hash,
+        offset) pairs on the device.  Returns the new tail.  Empty / NULL-byte
+        payloads fail as srd_batch_layout does; a batch that does not fit the
+        capacity raises ValueError before anything is written."""
+        import torch
+        n = len(payloads)
+        if len(hashes) != n:
+            raise ValueError("Mismatched lengths for key hashes and payloads.")
+        if not n:
+            return self._tail
+        payloads = [bytes(p) for p in payloads]
+        lens = np.array([len(p) for p in payloads], np.uint64)
+        # every payload at a 16-byte boundary of the staging blob: the writer moves
+        # whole 16-byte pieces of such sources
+        offs = np.zeros(n, np.uint64)
+        offs[1:] = np.cumsum((lens + np.uint64(15)) & ~np.uint64(15))[:-1]
+        blob = np.zeros(int(offs[-1] + lens[-1]) or 1, np.uint8)
+        for o, p in zip(offs, payloads):
+            blob[int(o): int(o) + len(p)] = np.frombuffer(p, np.uint8)
+        zero = np.zeros(n, np.uint64)
+        ent = (WriteEntry * n)()
+        nt = C.c_uint64()
+        _check(lib().srd_batch_layout(self._tail, _ptr(blob), _ptr(zero), _ptr(zero), _ptr(offs), _ptr(lens), n,
+                                      WRITE_ALLOW_NULL if allow_null else 0, C.cast(ent, C.c_void_p), C.byref(nt)))
+        new_tail = int(nt.value)
+        if padded_size(new_tail) > self.buf.numel():
+            raise ValueError(f"the batch ends at {new_tail}: beyond the store's capacity")
+        tomb = np.zeros(n, np.uint8)
+        for i, h in enumerate(hashes):  # batch_write_with_key_hashes: the keys are prehashed
+            ent[i].key_src = int(h)
+            ent[i].key_len = 0
+            tomb[i] = ent[i].flags & 1
+            ent[i].flags |= 2  # SRD_ENTRY_HASHED
+        dev = self.buf.device
+        d_ent = torch.from_numpy(np.frombuffer(ent, np.uint8).copy()).to(dev)
+        d_pay = torch.from_numpy(blob).to(dev)
+        d_kh = torch.empty(n, dtype=torch.int64, device=dev)
+        d_mo = torch.empty(n, dtype=torch.int64, device=dev)
+        base = self._tail & ~63
+        self.index._lib_after_torch()
+        _check(lib().srd_batch_write_device(self.ctx.h, C.c_void_p(d_pay.data_ptr()), C.c_void_p(d_pay.data_ptr()),
+                                            C.c_void_p(d_ent.data_ptr()), n, C.c_void_p(self.buf.data_ptr() + base),
+                                            base, C.c_void_p(d_kh.data_ptr()), C.c_void_p(d_mo.data_ptr()),
+                                            C.c_void_p(self.ctx.stream)))
+        self.index.apply(d_kh, d_mo, tomb if tomb.any() else None)  # same stream: behind the writer; waits
+        self._tail = new_tail
+        return new_tail
+
+    def batch_delete(self, keys) -> int:
+        """DataStoreWriter::batch_delete (data_store.rs:990-993)."""
+        return self.batch_delete_key_hashes(compute_hash_batch(keys, self.ctx))
+
+    def batch_delete_key_hashes(self, hashes) -> int:
+        """data_store.rs:995-1024: one tombstone per listed hash the index holds,
+        appended at the tail, and the keys removed from the index.  Returns the new tail."""
+        idx = self.index
+        q = idx._as_dev(hashes)
+        used, nt, nd = C.c_uint64(idx._used), C.c_uint64(), C.c_uint64()
+        idx._lib_after_torch()
+        rc = lib().srd_batch_delete_hashed_device(self.ctx.h, C.c_void_p(idx.table.data_ptr()), idx.nbytes,
+                                                  C.byref(used), C.c_void_p(q.data_ptr()), q.numel(), self._tail,
+                                                  C.c_void_p(self.buf.data_ptr()), self.buf.numel(), C.byref(nt),
+                                                  C.byref(nd))  # synchronises
+        if rc == SRD_ERR_ARG and "file_cap" in lib().srd_last_error().decode():
+            raise ValueError("the tombstones end beyond the store's capacity")
+        _check(rc)
+        idx._used = int(used.value)
+        if nd.value:
+            idx._live = None  # (duplicates in the list: the count of distinct keys is the table's)
+        self._tail = int(nt.value)
+        return self._tail
+
+    # -- reads ----------------------------------------------------------------------------
+
+    def _ranges(self, hashes, verify):
+        import torch
+        idx = self.index
+        q = idx._as_dev(hashes)
+        v = idx._as_dev(verify) if verify is not None else None
+        st, en = torch.empty_like(q), torch.empty_like(q)
+        idx._lib_after_torch()
+        _check(lib().srd_batch_read_hashed_device(self.ctx.h, C.c_void_p(idx.table.data_ptr()), idx.nbytes,
+                                                  C.c_void_p(self.buf.data_ptr()), self._tail, C.c_void_p(q.data_ptr()),
+                                                  C.c_void_p(v.data_ptr()) if v is not None else None, q.numel(),
+                                                  C.c_void_p(st.data_ptr()), C.c_void_p(en.data_ptr()),
+                                                  C.c_void_p(self.ctx.stream)))
+        idx._sync_lib()
+        return st.cpu().numpy().view(np.uint64), en.cpu().numpy().view(np.uint64)
+
+    def _payloads(self, st, en):
+        import torch
+        hit = [(int(a), int(b)) for a, b in zip(st, en) if a != b]
+        if not hit:
+            return [None] * len(st)
+        flat = torch.cat([self.buf[a:b] for a, b in hit]).cpu().numpy().tobytes()  # one copy to the host
+        out, o = [], 0
+        for a, b in zip(st, en):
+            if a == b:
+                out.append(None)
+            else:
+                out.append(flat[o: o + int(b - a)])
+                o += int(b - a)
+        return out
+
+    def batch_read(self, keys):
+        """DataStoreReader::batch_read (data_store.rs:1105-1109): [payload bytes | None];
+        every read verified by its key's own tag."""
+        if not len(keys):
+            return []
+        h = compute_hash_batch(keys, self.ctx)
+        return self._payloads(*self._ranges(h, h))
+
+    def batch_read_hashed_keys(self, hashes, non_hashed_keys=None):
+        """data_store.rs:1111-1158: with non_hashed_keys each read is verified by
+        tag_from_key (:513-521)."""
+        if non_hashed_keys is not None and len(non_hashed_keys) != len(hashes):
+            raise ValueError("Mismatched lengths for hashed and non-hashed keys.")
+        if not len(hashes):
+            return []
+        v = compute_hash_batch(non_hashed_keys, self.ctx) if non_hashed_keys is not None else None
+        return self._payloads(*self._ranges(hashes, v))
+
+    def read(self, key: bytes):
+        return self.batch_read([key])[0]
+
+    def exists(self, key: bytes) -> bool:
+        """DataStoreReader::exists (data_store.rs:1030-1032): read(key).is_some()."""
+        return self.read(key) is not None
