@@ -108,6 +108,47 @@ int srd_ctx_scan_loads(srd_ctx *ctx);
  * if not measured); returns the choice (0, 1) or -1 while still measuring
  * (or pinned by SRD_SCAN_LOADS, or with XCD-aware shares off). */
 int srd_ctx_scan_trial(srd_ctx *ctx, double *ms);
+/* Diagnostics: the optimistic scan's block partition, installed and read back.
+ * The scan's block b of n_blocks takes the resident spans [starts[b],
+ * starts[b + 1]) (16 KiB spans, relative to the first resident one).  Without
+ * a table that is the even split b * n_spans / n_blocks; with XCD-aware block
+ * shares (the default; SRD_XPART=0 at srd_ctx_create turns them off) every
+ * call measures its blocks and prepares the table of the next call on a store
+ * of the same resident span count and grid.
+ *
+ * srd_ctx_set_scan_blocks installs starts[0..n_blocks] as the table of the
+ * next optimistic scan, for that scan only (the scan prepares its successor's
+ * table as always); like a measured table it is ignored if that scan's
+ * resident span count or grid differ.  A valid table has 1 <= n_blocks <=
+ * 1024, starts[0] == 0, starts[n_blocks] == n_spans, non-decreasing starts
+ * (empty blocks are allowed anywhere) and no block larger than
+ * (5 n_spans + 4 n_blocks - 1) / (4 n_blocks) + 1 spans, the size the pass's
+ * workspace is laid out for.  Anything else, or a context with the shares off:
+ * SRD_ERR_ARG, nothing changed.
+ *
+ * srd_ctx_scan_blocks reads back SRD_SCAN_BLOCKS_LAST, the partition the
+ * last optimistic scan ran with (of a call that retried: its last attempt's;
+ * info->attempts counts that call's scans, info->first_source tells what the
+ * first one ran with), or SRD_SCAN_BLOCKS_NEXT, the table prepared for the
+ * next one.  info->source says where the starts come from; up to cap of the
+ * n_blocks + 1 starts are copied to starts.  info->n_blocks == 0: none (no
+ * scan yet / no table prepared).  Both entries wait for the context's stream. */
+#define SRD_SCAN_BLOCKS_LAST 0
+#define SRD_SCAN_BLOCKS_NEXT 1
+#define SRD_SCAN_BLOCKS_EVEN 0      /* source: no table, the even split */
+#define SRD_SCAN_BLOCKS_MEASURED 1  /* the table the previous scan's durations gave */
+#define SRD_SCAN_BLOCKS_INSTALLED 2 /* srd_ctx_set_scan_blocks */
+typedef struct {
+  uint64_t n_spans;
+  uint32_t n_blocks;
+  uint32_t source;
+  uint32_t attempts;
+  uint32_t first_source;
+} srd_scan_blocks_info;
+int srd_ctx_set_scan_blocks(srd_ctx *ctx, const uint64_t *starts,
+                            uint32_t n_blocks, uint64_t n_spans);
+int srd_ctx_scan_blocks(srd_ctx *ctx, int which, uint64_t *starts,
+                        uint32_t cap, srd_scan_blocks_info *info);
 const char *srd_last_error(void);
 /* The sha256 of the sources this library was compiled from (every .hip / .h /
  * .cpp file under csrc/ and include/srd_amd.h, as computed by
@@ -169,7 +210,9 @@ uint64_t srd_padded_size(uint64_t file_len);
 
 /* Device-resident validate+index over `file_len` bytes at `d_file`
  * (device pointer, 16-byte aligned, readable to srd_padded_size(file_len);
- * the bytes are the mmap'd store). */
+ * the bytes are the mmap'd store).  The call launches on the context's own
+ * non-blocking stream (srd_ctx_stream): the caller's writes to d_file must be
+ * complete, or ordered on that stream, before the call. */
 int srd_validate_index_device(srd_ctx *ctx, const uint8_t *d_file,
                               uint64_t file_len, uint32_t flags,
                               srd_device_result *out);

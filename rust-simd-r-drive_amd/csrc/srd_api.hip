@@ -5,6 +5,7 @@
 //
 //   device code
 //     srd_crc.h, srd_xxh3.h   CRC algebra / tables, XXH3-64
+//     srd_part.h              the scan's block / wave partition and its inverse (host code and a CPU check use it too)
 //     srd_kernels.hip         scan, link, full-pass glue, finalize, batch digests, synth
 //     srd_glue.hip            sync-free glue of the optimistic pass, bucketed index, owner partition
 //     srd_writer.hip          batch writer

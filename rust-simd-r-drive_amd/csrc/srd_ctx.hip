@@ -147,6 +147,17 @@ struct Ctx {
   bool xpart_on = true, xp_valid = false;
   uint32_t xp_par = 0, xp_g = 0;
   uint64_t xp_ns = 0;
+  // diagnostics (srd_ctx_set_scan_blocks / srd_ctx_scan_blocks): the table
+  // the next scan reads was installed by the caller; and what the last
+  // optimistic scan ran with -- its resident spans and grid, where its block
+  // starts came from (SRD_SCAN_BLOCKS_*) and the half of XPart::bs it read
+  bool xp_installed = false;
+  struct LastPart {
+    bool any = false;
+    uint64_t ns = 0;
+    uint32_t g = 0, src = 0, par = 0;
+    uint32_t attempts = 0, first_src = 0;  // of the call that scan belonged to: its scans, the first one's source
+  } xp_last;
   srd_device_result res{};
   // host-input staging
   Buf file;
@@ -587,6 +598,64 @@ extern "C" int srd_ctx_scan_trial(srd_ctx* c, double* ms) {
   if (ms)
     for (int k = 0; k < 2; k++) ms[k] = c->tune.n[k] ? (double)c->tune.best[k] * 1e-5 : 0.0;  // 10 ns ticks
   return c->tune.choice;
+}
+// The block-start table of the optimistic scan, installed and read back
+// (diagnostics: tests pin the partition a call runs on instead of taking
+// whatever the box's timing history produced).  The copies go through the
+// context's stream, behind the previous call's link2 and in front of the next
+// call's scan, and are waited for.
+extern "C" int srd_ctx_set_scan_blocks(srd_ctx* c, const uint64_t* starts, uint32_t n_blocks, uint64_t n_spans) {
+  if (!c || !starts) { set_err("bad argument"); return SRD_ERR_ARG; }
+  if (!c->xpart_on) { set_err("XCD-aware block shares are off on this context (SRD_XPART=0)"); return SRD_ERR_ARG; }
+  if (!part_table_ok(starts, n_blocks, n_spans)) {
+    set_err("bad argument: not a block-start table of n_blocks blocks over n_spans spans (srd_ctx_set_scan_blocks)");
+    return SRD_ERR_ARG;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  TRY(ensure_z(c, B_XPART, sizeof(XPart)));
+  HIPCHK(hipMemcpyAsync(&P<XPart>(c, B_XPART)->bs[c->xp_par][0], starts, ((size_t)n_blocks + 1) * 8,
+                        hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->xp_valid = true;
+  c->xp_installed = true;
+  c->xp_ns = n_spans;
+  c->xp_g = n_blocks;
+  return 0;
+}
+extern "C" int srd_ctx_scan_blocks(srd_ctx* c, int which, uint64_t* starts, uint32_t cap,
+                                   srd_scan_blocks_info* info) {
+  if (!c || !info || (cap && !starts) || (which != SRD_SCAN_BLOCKS_LAST && which != SRD_SCAN_BLOCKS_NEXT)) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  *info = srd_scan_blocks_info{};
+  const Ctx::LastPart& l = c->xp_last;
+  uint32_t par = 0;
+  if (which == SRD_SCAN_BLOCKS_LAST) {
+    if (!l.any) return 0;
+    info->n_spans = l.ns;
+    info->n_blocks = l.g;
+    info->source = l.src;
+    info->attempts = l.attempts;
+    info->first_source = l.first_src;
+    par = l.par;
+  } else {
+    if (!c->xp_valid) return 0;
+    info->n_spans = c->xp_ns;
+    info->n_blocks = c->xp_g;
+    info->source = c->xp_installed ? SRD_SCAN_BLOCKS_INSTALLED : SRD_SCAN_BLOCKS_MEASURED;
+    par = c->xp_par;
+  }
+  const size_t n = std::min<size_t>(cap, (size_t)info->n_blocks + 1);
+  if (!n) return 0;
+  if (info->source == SRD_SCAN_BLOCKS_EVEN) {
+    for (size_t b = 0; b < n; b++) starts[b] = b * info->n_spans / info->n_blocks;
+    return 0;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipMemcpyAsync(starts, &P<XPart>(c, B_XPART)->bs[par][0], n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
 }
 extern "C" uint64_t srd_ctx_device_bytes(srd_ctx* c) {
   if (!c) return 0;

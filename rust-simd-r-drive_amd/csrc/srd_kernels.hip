@@ -28,6 +28,7 @@
 
 #include "srd_crc.h"
 #include "srd_xxh3.h"
+#include "srd_part.h"
 
 namespace srd {
 
@@ -86,26 +87,6 @@ __device__ uint64_t g_wave_clk[4096 + 256];  // s_memtime (shader clock) at wave
                                                 // XCC_ID; [8192 + 1023]: the epilogue's end
 #endif
 
-// The scan's wave partition (both passes; link_record inverts it).  Block b of g
-// takes the resident spans [st(b), st(b+1)), st(b) = b*ns/g; inside a block
-// wave v takes the share [cw(v), cw(v+1)) (units of 1/65536) of the block's
-// spans.  Waves of one SIMD do not progress equally: the SIMD issues for
-// its oldest waves first, so with an even split waves 0-3 (the oldest on
-// each SIMD) finished ~15% before waves 12-15 (tools/wave_stamps.py); the
-// per-slot shares wq[v] (scan_weights: fitted to the wave stamps) even out
-// the finish times.  The optimistic pass replaces st(b) by a device table
-// (XPart, XCD-aware block shares) once a context has scanned a store of the
-// same span count and grid.
-struct ScanPart {
-  uint64_t s_lo;   // first resident span
-  uint64_t ns;     // resident spans
-  uint32_t g;      // scan blocks
-  uint32_t nw;     // waves per scan block (<= 16; the launch's variant sets it, scan_geom)
-  uint32_t wq[16];  // share of wave slot v of each block; wq[0] + .. + wq[nw-1] == 65536
-  uint32_t cw[17];  // cumulative: cw[v] = wq[0] + .. + wq[v-1] (part_fill_cw)
-  const uint64_t* bs;  // device: st(0..g) (XPart::bs of this call), nullptr: st(b) = b*ns/g
-};
-
 // XCD-aware block shares (the optimistic scan).  The dispatcher hands block b
 // to XCD (b + r) mod 8, r fixed per HW queue, and the XCDs do not stream at
 // one speed: on a box the odd XCDs ran their blocks 4-5 % slower than the even
@@ -118,7 +99,6 @@ struct ScanPart {
 // the other half of a double-buffered table: call k reads bs[k & 1], writes
 // bs[(k + 1) & 1] (the host flips the parity; it uses the table only for the
 // span count and grid it was made for).
-constexpr uint32_t XP_MAX_BLOCKS = 1024;
 constexpr float XP_CLAMP = 0.10f;
 struct XPart {
   uint64_t bs[2][XP_MAX_BLOCKS + 1];  // block starts (resident-relative spans) per parity
@@ -128,43 +108,6 @@ struct XPart {
   float w[8];                         // each XCD's relative speed (0: none measured yet)
   uint64_t scan_ticks;                // the last scan: first block start -> last block end (idx_emit publishes it)
 };
-__host__ __device__ __forceinline__ void part_fill_cw(ScanPart& p) {
-  p.cw[0] = 0;
-  for (uint32_t v = 0; v < 16; v++) p.cw[v + 1] = p.cw[v] + (v < p.nw ? p.wq[v] : 0u);
-}
-// cumulative share of the waves below v (v <= 16)
-__host__ __device__ __forceinline__ uint64_t part_cw(const ScanPart& p, uint32_t v) { return p.cw[v]; }
-__host__ __device__ __forceinline__ uint64_t part_block_start(const ScanPart& p, uint64_t b) {
-  if (p.bs) return p.bs[b];  // (device pointer: host code sizes with the even split, bs unset)
-  return b * p.ns / p.g;
-}
-// wave v of block b: resident-relative spans [*r0, *r1)
-__host__ __device__ __forceinline__ void part_wave_range(const ScanPart& p, uint64_t b, uint32_t v,
-                                                         uint64_t* r0, uint64_t* r1) {
-  const uint64_t bs = part_block_start(p, b), nb = part_block_start(p, b + 1) - bs;
-  *r0 = bs + ((nb * part_cw(p, v)) >> 16);
-  *r1 = bs + ((nb * part_cw(p, v + 1)) >> 16);
-}
-// the scan wave (b * nw + v) holding resident-relative span rel < ns
-__device__ __forceinline__ uint64_t part_span_wave(const ScanPart& p, uint64_t rel) {
-  uint64_t b;
-  if (p.bs) {  // the last block whose start is <= rel (empty blocks are skipped over)
-    uint64_t lo = 0, hi = p.g - 1;
-    while (lo < hi) {
-      const uint64_t mid = (lo + hi + 1) >> 1;
-      if (p.bs[mid] <= rel) lo = mid; else hi = mid - 1;
-    }
-    b = lo;
-  } else {
-    b = rel * p.g / p.ns;
-    while (b + 1 < p.g && part_block_start(p, b + 1) <= rel) b++;
-  }
-  const uint64_t bs = part_block_start(p, b), nb = part_block_start(p, b + 1) - bs, o = rel - bs;
-  uint32_t v = 0;
-#pragma unroll
-  for (uint32_t j = 1; j < 16; j++) v += j < p.nw && o >= ((nb * part_cw(p, j)) >> 16) ? 1u : 0u;
-  return b * p.nw + v;
-}
 
 struct ScanArgs {
   ScanPart part;

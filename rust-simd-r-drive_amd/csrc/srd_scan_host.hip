@@ -75,15 +75,7 @@ static ScanPart scan_part(const Ctx* c, uint64_t s_lo, uint64_t ns, unsigned g, 
   part_fill_cw(p);
   return p;
 }
-// an upper bound on the spans of one wave; xpart: with XCD-aware block
-// shares, a block holds at most (1 + XP_CLAMP) / (1 - XP_CLAMP) < 1.25 of
-// the even share + 1 span (xpart_update)
-static uint64_t part_max_wave_spans(const ScanPart& p, bool xpart = false) {
-  if (!p.g) return 1;
-  const uint32_t wmax = *std::max_element(p.wq, p.wq + p.nw);
-  const uint64_t nb = xpart ? (p.ns * 5 + 4 * p.g - 1) / (4 * p.g) + 1 : (p.ns + p.g - 1) / p.g;
-  return (nb * wmax + 65535) / 65536 + 1;
-}
+// (part_max_wave_spans, the bound on the spans of one wave: srd_part.h)
 
 static int alloc_scan(Ctx* c, uint64_t n_tiles, uint64_t n_spans, uint32_t cap) {
   const uint64_t slots = n_spans * cap;

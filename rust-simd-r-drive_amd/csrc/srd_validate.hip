@@ -512,6 +512,16 @@ static int optimistic_pass(Ctx* c, const uint8_t* d_span, uint64_t span_off, uin
       // the table the previous scan's link2 wrote, if it was made for this span count and grid
       if (c->xp_valid && c->xp_ns == ns_rel && c->xp_g == g) part.bs = &o.xp->bs[c->xp_par][0];
     }
+    {  // what this scan runs with (srd_ctx_scan_blocks)
+      Ctx::LastPart& l = c->xp_last;
+      l.any = true;
+      l.ns = ns_rel;
+      l.g = g;
+      l.par = c->xp_par;
+      l.src = !part.bs ? SRD_SCAN_BLOCKS_EVEN : c->xp_installed ? SRD_SCAN_BLOCKS_INSTALLED : SRD_SCAN_BLOCKS_MEASURED;
+      l.attempts = attempt + 1;
+      if (!attempt) l.first_src = l.src;
+    }
     o.total_waves = (uint64_t)g * nw;
     const uint64_t spw = part_max_wave_spans(part, xpart);
     o.wcap = spw * c->copt.cap;
@@ -546,6 +556,7 @@ static int optimistic_pass(Ctx* c, const uint8_t* d_span, uint64_t span_off, uin
     if (o.xp) {  // link2 wrote the next call's block starts into the other half
       c->xp_par ^= 1u;
       c->xp_valid = true;
+      c->xp_installed = false;
       c->xp_ns = ns_rel;
       c->xp_g = g;
     }

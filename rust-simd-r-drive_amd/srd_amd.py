@@ -41,6 +41,8 @@ SRD_MODE_SPAN_UNPROVEN = 3
 SRD_FULL_NONE, SRD_FULL_FORCED, SRD_FULL_SLOT_SPACE, SRD_FULL_WAVES = 0, 1, 2, 3
 SRD_FULL_NO_START, SRD_FULL_UNPROVEN, SRD_FULL_CAP, SRD_FULL_LOOKBACK = 4, 5, 6, 7
 SRD_ERR_ARG, SRD_ERR_FULL = -3, -5
+SCAN_BLOCKS_LAST, SCAN_BLOCKS_NEXT = 0, 1  # srd_ctx_scan_blocks: which partition
+SCAN_BLOCKS_EVEN, SCAN_BLOCKS_MEASURED, SCAN_BLOCKS_INSTALLED = 0, 1, 2  # srd_scan_blocks_info.source
 SRD_FLAG_MERGE_INDEX = 16  # multi-GPU open: the whole index on ctxs[0] (default: by owner)
 SRD_MULTI_COMPOSED, SRD_MULTI_NEIGHBOUR, SRD_MULTI_WHOLE_FILE = 0, 1, 2  # srd_multi_summary.path
 SPAN_ALIGN = 16384  # span_off granularity of srd_validate_span_device
@@ -52,7 +54,7 @@ OFFSET_MASK = (1 << 48) - 1
 # symbols include/srd_amd.h declares
 EXPORTS = [
     "srd_ctx_create", "srd_ctx_destroy", "srd_ctx_stream", "srd_ctx_device_bytes", "srd_ctx_scan_loads",
-    "srd_ctx_scan_trial",
+    "srd_ctx_scan_trial", "srd_ctx_set_scan_blocks", "srd_ctx_scan_blocks",
     "srd_last_error", "srd_build_info",
     "srd_ctx_timings",
     "srd_ctx_set_timing",
@@ -82,6 +84,12 @@ class DeviceResult(C.Structure):
         ("crc_stored", C.c_void_p), ("crc_computed", C.c_void_p), ("crc_ok", C.c_void_p),
         ("index_key_hash", C.c_void_p), ("index_packed", C.c_void_p),
     ]
+
+
+class ScanBlocksInfo(C.Structure):
+    """srd_scan_blocks_info (include/srd_amd.h)"""
+    _fields_ = [("n_spans", C.c_uint64), ("n_blocks", C.c_uint32), ("source", C.c_uint32),
+                ("attempts", C.c_uint32), ("first_source", C.c_uint32)]
 
 
 class MultiSummary(C.Structure):
@@ -139,6 +147,8 @@ def lib():
         L.srd_ctx_device_bytes.restype = u64
         L.srd_ctx_scan_loads.argtypes = [vp]
         L.srd_ctx_scan_trial.argtypes = [vp, C.POINTER(C.c_double)]
+        L.srd_ctx_set_scan_blocks.argtypes = [vp, vp, u32, u64]
+        L.srd_ctx_scan_blocks.argtypes = [vp, i32, vp, u32, C.POINTER(ScanBlocksInfo)]
         if not os.environ.get("SRD_LIB_PATH"):  # (timing tools load variant builds by path)
             import importlib.util
             spec = importlib.util.spec_from_file_location("srd_src_hash", os.path.join(HERE, "src_hash.py"))
@@ -266,6 +276,23 @@ class Context:
         ms = (C.c_double * 2)()
         ch = int(lib().srd_ctx_scan_trial(self.h, ms))
         return ch, float(ms[0]), float(ms[1])
+
+    def set_scan_blocks(self, starts, n_spans: int):
+        """srd_ctx_set_scan_blocks: install starts[0..n_blocks] as the block-start table of the next
+        optimistic scan (diagnostics); SrdError (SRD_ERR_ARG) outside the table domain or with the shares off."""
+        st = np.ascontiguousarray(starts, dtype=np.uint64)
+        _check(lib().srd_ctx_set_scan_blocks(self.h, C.c_void_p(st.ctypes.data), max(st.size, 1) - 1, n_spans))
+
+    def scan_blocks(self, which: int = SCAN_BLOCKS_LAST):
+        """srd_ctx_scan_blocks: (starts [n_blocks + 1] u64, ScanBlocksInfo) of the partition the last optimistic
+        scan ran with (SCAN_BLOCKS_LAST) or of the table prepared for the next one (SCAN_BLOCKS_NEXT);
+        info.n_blocks == 0 and no starts: none."""
+        info = ScanBlocksInfo()
+        _check(lib().srd_ctx_scan_blocks(self.h, which, None, 0, C.byref(info)))
+        st = np.zeros(info.n_blocks + 1 if info.n_blocks else 0, np.uint64)
+        if st.size:
+            _check(lib().srd_ctx_scan_blocks(self.h, which, C.c_void_p(st.ctypes.data), st.size, C.byref(info)))
+        return st, info
 
     def timings(self):
         """(scan_ms, scan_launches) summed over the validate calls since the last

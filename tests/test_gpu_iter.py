@@ -66,6 +66,7 @@ def validated(ctx, f):
     import torch
     dev = torch.zeros(S.padded_size(len(f)), dtype=torch.uint8, device="cuda")
     dev[: len(f)] = torch.frombuffer(bytearray(f), dtype=torch.uint8).cuda()
+    torch.cuda.synchronize()  # the library launches on its own stream, not ordered behind torch's
     r = S.validate_index_device(dev.data_ptr(), len(f), 0, ctx)
     assert r.final_len == len(f)
     return dev, r

@@ -83,6 +83,7 @@ def to_dev(f, extra=0):
     import torch
     dev = torch.zeros(S.padded_size(len(f) + extra), dtype=torch.uint8, device="cuda")
     dev[: len(f)] = torch.frombuffer(bytearray(f), dtype=torch.uint8).cuda()
+    torch.cuda.synchronize()  # the library launches on its own stream, not ordered behind torch's
     return dev
 
 

@@ -305,6 +305,7 @@ def test_full_c4_eight_shards():
         i = 5 * per + 12345
         pos = 4160 * i + 777 - soffs[5]
         keep[5][pos] ^= 0x40
+        torch.cuda.synchronize()  # the library launches on its own streams, not ordered behind torch's
         shards, sm = S.validate_index_multi_device(cs, spans, soffs, cuts)
         assert (sm.path, sm.final_len, sm.n_chain, sm.n_crc_bad) == (S.SRD_MULTI_COMPOSED, C4_LEN, C4_N, 1)
         ok = S.device_view(shards[5].crc_ok, shards[5].n_chain, np.uint8)

@@ -559,16 +559,26 @@ def test_full_size_c2_properties(ctx):
     ln = S.device_to_numpy(r.payload_len, n, np.uint64)
     crc = S.device_to_numpy(r.crc_computed, n, np.uint32)
     assert np.array_equal(O.crc32_ranges(host, mo - ln, ln, threads=16), crc)
-    del ik, iv, keys, packed, mo, ln, crc
+    del ik, iv, keys, packed, mo, ln
     # flip one payload byte deep in the store -> exactly one bad CRC
     pos = 4160 * 777_777 + 1234
     t[pos] ^= 0x40
+    torch.cuda.synchronize()  # the library launches on its own stream, not ordered behind torch's
     r = S.validate_index_device(t.data_ptr(), size, 0, ctx)
     assert (r.final_len, r.n_chain, r.n_crc_bad) == (size, n, 1)
+    # ... and it is entry 777777's, computed over the flipped payload; no other entry's value moved (a
+    # stale tile value or a span no wave scanned would leave the old CRC in place: n_crc_bad == 0)
+    host[pos] ^= 0x40
+    crc2 = S.device_to_numpy(r.crc_computed, n, np.uint32)
+    ok2 = S.device_to_numpy(r.crc_ok, n, np.uint8)
+    assert ok2[777_777] == 0
+    assert int(crc2[777_777]) == zlib.crc32(host[4160 * 777_777: 4160 * 777_777 + 4096].tobytes())
+    crc2[777_777] = crc[777_777]
+    assert np.array_equal(crc2, crc)
+    del crc, crc2, ok2
     # torn tail: drop the last 100 bytes -> oracle decides final_len
     cut = size - 100
     r = S.validate_index_device(t.data_ptr(), cut, 0, ctx)
-    host[pos] ^= 0x40
     assert r.final_len == O.recover_valid_chain(host[:cut])
 
 
@@ -681,6 +691,7 @@ def test_index_build_device_hot_key(ctx):
     keys = [0xABCDEF if rnd.random() < 0.7 else rnd.getrandbits(64) for _ in range(7000)]
     pairs = np.array([[k, 64 * i + 7] for i, k in enumerate(keys)], np.uint64).reshape(-1)
     d = torch.from_numpy(pairs.view(np.int64)).cuda()
+    torch.cuda.synchronize()  # the library launches on its own stream, not ordered behind torch's
     ok = torch.empty(7000, dtype=torch.int64, device="cuda")
     op = torch.empty(7000, dtype=torch.int64, device="cuda")
     n = S.index_build_device(d.data_ptr(), 7000, ok.data_ptr(), op.data_ptr(), ctx)

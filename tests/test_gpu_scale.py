@@ -62,6 +62,7 @@ def _span_result(ctx, lens, seed=0x5EED0007):
     lo, hi = S.synth_span(None, 0, 1, n, 0, lens)
     assert lo % S.SPAN_ALIGN == 0
     t = torch.zeros(S.padded_size(hi - lo), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()  # the library launches on its own stream, not ordered behind torch's
     S.synth_span(t.data_ptr(), lo, 1, n, 0, lens, seed=seed, ctx=ctx)
     torch.cuda.synchronize()
     r = S.validate_span_device(t.data_ptr(), lo, lo, hi, 0, ctx)
@@ -207,6 +208,7 @@ def test_full_c3_properties(ctx):
     big = int(np.nonzero(ln > (1 << 19))[0][len(np.nonzero(ln > (1 << 19))[0]) // 2])
     pos = int(mo[big]) - 12345
     t[pos] ^= 0x08
+    torch.cuda.synchronize()  # the library launches on its own stream, not ordered behind torch's
     r = S.validate_index_device(t.data_ptr(), size, 0, ctx)
     assert (r.final_len, r.n_chain, r.n_crc_bad) == (size, n, 1)
     ok = S.device_to_numpy(r.crc_ok, n, np.uint8)
@@ -283,6 +285,7 @@ def test_overflow_after_large_call_one_context():
                 n = 5_000_000
                 size = S.synth_store_len(n, 8)
                 d = torch.zeros(S.padded_size(size), dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()  # the library launches on its own stream, not ordered behind torch's
                 S.synth_store_device(d.data_ptr(), n, 8, ctx=c)
                 torch.cuda.synchronize()
                 store = d[:size].cpu().numpy()

@@ -29,6 +29,7 @@ def _worker(rank, world, port, n_total, q):
         lo, hi = S.synth_span(None, 0, first, cnt, 1000)
         span_off = lo - lo % S.SPAN_ALIGN
         buf = torch.zeros(S.padded_size(hi - span_off), dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()  # the library launches on its own stream, not ordered behind torch's
         S.synth_span(buf.data_ptr(), span_off, first, cnt, 1000, ctx=ctx)
         res = SH.sharded_validate_index(SH.HipBackend(ctx, 0), buf, span_off, lo, hi, S.synth_store_len(n_total, 1000))
         q.put((rank, res.composed, res.final_len, res.n_chain, res.n_crc_bad, res.n_index,

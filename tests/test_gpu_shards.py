@@ -154,6 +154,7 @@ def test_synth_span_matches_whole_store(ctx):
         lo, hi = S.synth_span(None, 0, first, cnt)
         span_off = lo - lo % S.SPAN_ALIGN
         t = torch.zeros(S.padded_size(hi - span_off), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()  # the library launches on its own stream, not ordered behind torch's
         assert S.synth_span(t.data_ptr(), span_off, first, cnt, ctx=ctx) == (lo, hi)
         assert torch.equal(t[: hi - span_off], whole[span_off:hi]), (first, cnt)
         r = S.validate_span_device(t.data_ptr(), span_off, lo, hi, 0, ctx)

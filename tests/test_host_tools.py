@@ -34,6 +34,19 @@ def test_sanitizer_harness():
     assert p.returncode == 0 and "host_fuzz ok" in p.stdout, p.stderr[-3000:]
 
 
+def test_scan_partition_arithmetic_sanitized():
+    """csrc/srd_part.h (the scan's block / wave partition and its inverse, the code the kernels run) as a
+    stand-alone host program under ASan + UBSan: the wave ranges tile the resident spans, part_span_wave
+    inverts them for every span, no wave exceeds the bound the workspace is sized by -- over seeded random
+    stores, every wave-share set of test_scan_wave_shares and block-start tables from the whole domain of
+    srd_ctx_set_scan_blocks (tests/sanitize/part_check.cpp)."""
+    d = os.path.join(ROOT, "tests", "sanitize")
+    subprocess.check_call(["make", "-s", "-C", d, "build/part_check"])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    p = subprocess.run([os.path.join(d, "build", "part_check")], capture_output=True, text=True, env=env, timeout=600)
+    assert p.returncode == 0 and "part_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
+
+
 def _abi_check_bin():
     d = os.path.join(ROOT, "tests", "abi_c")
     if not os.path.exists(S.LIB_PATH):
