@@ -6,8 +6,10 @@
 //   device code
 //     srd_crc.h, srd_xxh3.h   CRC algebra / tables, XXH3-64
 //     srd_part.h              the scan's block / wave partition and its inverse (host code and a CPU check use it too)
-//     srd_kernels.hip         scan, link, full-pass glue, finalize, batch digests, synth
-//     srd_glue.hip            sync-free glue of the optimistic pass, bucketed index, owner partition
+//     srd_fin.h               the finalize rule: an entry's CRC from the scan's pieces, the byte-table multiply
+//                             (both passes, the slow path, the writer, the host self-test and a CPU check)
+//     srd_kernels.hip         scan, link, full-pass glue, finalize (one entry: finalize_in), slow path, batch digests, synth
+//     srd_glue.hip            sync-free glue of the optimistic pass (shape test, entry pass), bucketed index, owner partition
 //     srd_writer.hip          batch writer
 //     srd_index.hip           lookup table, batched reads, iterator, compaction
 //     srd_index_live.hip      the table kept live: apply, export, batched delete
@@ -93,44 +95,29 @@ extern "C" int srd_debug_wave_clk(uint64_t* out) {
 }
 #endif
 
-// host self-test of the CRC algebra (no GPU): checks the tables against a
-// byte-wise CRC on pseudo-random data with the same combine the kernels use.
+// host self-test of the CRC algebra (no GPU): the tables and the combine the
+// kernels run (srd_fin.h), against a byte-wise CRC on pseudo-random data.
+// (tests/sanitize/fin_check.cpp sweeps the rule's every branch.)
 extern "C" int srd_selftest_host(void) {
   const CrcTables& t = host_tabs();
+  const FinTabs ft = fin_tabs_host(t);
   static uint8_t buf[5 * 4096];
   memset(buf, 0, sizeof buf);
   uint64_t z = 12345;
   for (int i = 0; i < 3 * 4096 + 200; i++) { auto& b = buf[i]; z = z * 6364136223846793005ull + 1442695040888963407ull; b = (uint8_t)(z >> 56); }
   // x^-8 * x^8 == 1
   if (mulp(t.invpow[1], t.pow8[0]) != kX0) return 1;
-  // check crc_from_pieces-style assembly for several (s, m)
   auto raw = [&](uint64_t a, uint64_t b) { return host_crc_raw_bytes(t, 0, buf + a, b - a); };
-  auto crc32 = [&](uint64_t a, uint64_t b) { return ~host_crc_raw_bytes(t, ~0u, buf + a, b - a); };
-  auto sx = [&](uint64_t k, uint32_t j) {  // crc_raw(lines j..63 of tile k)
-    return raw(k * 4096 + 64 * j, k * 4096 + 4096);
-  };
+  struct { uint32_t v[4]; uint32_t operator[](int i) const { return v[i]; } } tile[5];
+  for (uint64_t k = 0; k < 5; k++)  // what the scan records per tile: lines 0..31, 1..31, 32..63
+    tile[k] = {{raw(k * 4096, k * 4096 + 2048), raw(k * 4096 + 64, k * 4096 + 2048), raw(k * 4096 + 2048, k * 4096 + 4096), 0}};
+  auto sx = [&](uint64_t o) { return raw(o & ~63ull, (o | 4095) + 1); };  // crc_raw(o's line .. its tile's end)
   const uint64_t cases[][2] = {{0, 100}, {64, 4096}, {128, 5000}, {4096, 8192 + 77}, {192, 12288 + 3}, {0, 63}};
   for (auto& cs : cases) {
-    uint64_t s = cs[0], m = cs[1];
-    uint64_t len = m - s;
-    uint32_t want = crc32(s, m);
-    uint32_t tail = raw(m & ~63ull, m);
-    uint32_t got;
-    if (len < 64) {
-      got = tail ^ t.zero_crc[len];
-    } else {
-      uint64_t k0 = s / 4096, k1 = m / 4096;
-      uint32_t acc = sx(k0, (uint32_t)((s % 4096) / 64)) ^ t.winit[(s % 4096) / 64];
-      uint32_t sxm = sx(k1, (uint32_t)((m % 4096) / 64));
-      uint32_t y;
-      if (k0 == k1) y = acc ^ sxm;
-      else {
-        for (uint64_t k = k0 + 1; k < k1; k++) acc = mulp(t.x32768, acc) ^ sx(k, 0);
-        y = mulp(t.x32768, acc) ^ sx(k1, 0) ^ sxm;
-      }
-      got = ~(mulp(t.invpow[(k1 + 1) * 4096 - m], y) ^ tail);
-    }
-    if (got != want) return 2;
+    const uint64_t s = cs[0], m = cs[1];
+    const uint32_t want = ~host_crc_raw_bytes(t, ~0u, buf + s, m - s), tail = raw(m & ~63ull, m);
+    if (crc_from_pieces(s, m, sx(s), sx(m), tail, tile, ft) != want) return 2;
+    if (crc_from_pieces4(s, m, sx(s), sx(m), tail, tile, tile[m / 4096], ft) != want) return 3;
   }
   return 0;
 }

@@ -51,7 +51,17 @@ struct CrcTables {
   uint32_t x32768;          // x^(8*4096)       one tile
   uint32_t pow8[64];        // x^(8*2^k)
   uint32_t invpow[4097];    // x^(-8d), d = 0..4096
+  // fixed-multiplier byte tables (fill_mul_table; srd_fin.h's mulfix reads them)
+  uint32_t m16k[4][256];    // v -> v * x^16384 (half a tile)
+  uint32_t m32k[4][256];    // v -> v * x^32768 (one tile step in one multiply)
+  uint32_t mtk[3][4][256];  // v -> v * x^(32768 (j + 2)): 2-4 tile steps in one multiply
 };
+
+// m[256 k + b] = f * (b << 8k): v * f is the XOR of four lookups, one per byte of v
+inline void fill_mul_table(uint32_t* m, uint32_t f) {
+  for (int k = 0; k < 4; k++)
+    for (uint32_t b = 0; b < 256; b++) m[256 * k + b] = mulp(f, b << (8 * k));
+}
 
 inline uint32_t host_crc_raw_bytes(const CrcTables& t, uint32_t s, const uint8_t* p, uint64_t n) {
   for (uint64_t i = 0; i < n; i++) s = t.tab[0][(s ^ p[i]) & 0xff] ^ (s >> 8);
@@ -95,6 +105,9 @@ inline void build_crc_tables(CrcTables& t) {
   for (int i = 0; i < 8; i++) xinv8 = mulp(xinv, xinv8);
   t.invpow[0] = kX0;
   for (int d = 1; d <= 4096; d++) t.invpow[d] = mulp(xinv8, t.invpow[d - 1]);
+  fill_mul_table(&t.m16k[0][0], host_xpow8(t, 2048));
+  fill_mul_table(&t.m32k[0][0], t.x32768);
+  for (int j = 0; j < 3; j++) fill_mul_table(&t.mtk[j][0][0], host_xpow8(t, 4096 * (j + 2)));
 }
 
 }  // namespace srd

@@ -293,22 +293,21 @@ int upload_tables() {
     for (int b = 0; b < 256; b++) t.mx64[tb][b] = mulp(t.xtile[64], (uint32_t)b << (8 * tb));
   memcpy(t.pow8, ht.pow8, sizeof t.pow8);
   memcpy(t.invpow, ht.invpow, sizeof t.invpow);
+  memcpy(t.m16k, ht.m16k, sizeof t.m16k);
+  memcpy(t.m32k, ht.m32k, sizeof t.m32k);
+  memcpy(t.mtk, ht.mtk, sizeof t.mtk);
   for (int pos = 0; pos < 8; pos++)
     for (int nb = 0; nb < 16; nb++)
       for (int l = 0; l < 32; l++)  // x^(512*(31-l)) = lw[l + 32]
         t.nib[((pos * 16 + nb) << 5) + l] = mulp(ht.lw[l + 32], (uint32_t)nb << (4 * pos));
   {
-    const uint32_t x16k = host_xpow8(ht, 2048);
     for (int tb = 0; tb < 4; tb++)
       for (int b = 0; b < 256; b++) {
-        t.m16k[tb][b] = mulp(x16k, (uint32_t)b << (8 * tb));
         for (int q = 0; q < 3; q++) {
           t.last[q][tb][b] = mulp(host_xpow8(ht, 4 + 16 * (3 - q)), (uint32_t)b << (8 * tb));
           t.last_c[q][tb][b] = mulp(host_xpow8(ht, 4 + 1024 * (3 - q)), (uint32_t)b << (8 * tb));
         }
         t.m4096[tb][b] = mulp(host_xpow8(ht, 512), (uint32_t)b << (8 * tb));
-        t.m32k[tb][b] = mulp(ht.x32768, (uint32_t)b << (8 * tb));
-        for (int j = 0; j < 3; j++) t.mtk[j][tb][b] = mulp(host_xpow8(ht, 4096 * (j + 2)), (uint32_t)b << (8 * tb));
       }
     for (int pos = 0; pos < 8; pos++)
       for (int nb = 0; nb < 16; nb++)

@@ -329,6 +329,23 @@ __global__ __launch_bounds__(256) void child2_kernel(ShapeArgs a) {
 // follows back-pointers from file_len (data_store.rs:404-470).  Round 0
 // reads the link phase's claims (core: (childof[g] >> 32) == gen); the retry
 // rounds, the prune marks and child2's core-only claims.
+//
+// The test of one record g: its parent p (d_par[g]), p's own parent pp and
+// claim word cp; linked(false) / linked(true): something links to g / to p;
+// is_start(node) tells the start node.  SHAPE_LEAF: g is not core; the rest
+// are core: SHAPE_ROOT links to a root (what that does is the caller's: rule
+// (3)), SHAPE_FAIL breaks rule (1) or (2).
+enum Shape { SHAPE_LEAF, SHAPE_CORE, SHAPE_ROOT, SHAPE_FAIL };
+template <class Linked, class IsStart>
+__device__ __forceinline__ Shape shape_test(uint32_t gen, uint64_t g, int64_t p, int64_t pp, uint64_t cp, Linked linked,
+                                            IsStart is_start) {
+  if (!(is_start(g) || (linked(false) && (p >= 0 || p == PAR_ROOT)))) return SHAPE_LEAF;  // is_core(g)
+  if (p == PAR_ROOT) return SHAPE_ROOT;
+  // dangling: the chain through g is broken (only the start node can get here)
+  if (p < 0 || !(is_start((uint64_t)p) || (linked(true) && (pp >= 0 || pp == PAR_ROOT)))) return SHAPE_FAIL;
+  // branch: another node holds the claim on the same parent
+  return cp != claim_word(gen, g) ? SHAPE_FAIL : SHAPE_CORE;
+}
 __global__ __launch_bounds__(CHAIN_THREADS) void check_kernel(ShapeArgs a) {
   __shared__ uint32_t wsum[CHAIN_WAVES];
   __shared__ uint32_t s_pre[BW_MAX + 1];
@@ -371,21 +388,20 @@ __global__ __launch_bounds__(CHAIN_THREADS) void check_kernel(ShapeArgs a) {
 #pragma unroll
     for (int r = 0; r < CR; r++) {
       if (!in[r]) break;
-      const int64_t p = par[r];
-      const bool linked = marks ? hc[r] == a.gen : (cg[r] & ~0xffffffffull) == tag;
-      const bool core = g[r] == start || (linked && (p >= 0 || p == PAR_ROOT));  // is_core(g)
-      GST(a.flag[g[r]], (uint8_t)core);
-      if (!core) continue;
+      const Shape s = shape_test(
+          a.gen, g[r], par[r], pp[r], cp[r],
+          [&](bool parent) {  // round 0: the link phase's claims; the retry rounds: the prune marks
+            return marks ? (parent ? hp[r] : hc[r]) == a.gen : ((parent ? cp[r] : cg[r]) & ~0xffffffffull) == tag;
+          },
+          [&](uint64_t node) { return node == start; });
+      GST(a.flag[g[r]], (uint8_t)(s != SHAPE_LEAF));
+      if (s == SHAPE_LEAF) continue;
       cnt++;
-      const bool plinked = marks ? hp[r] == a.gen : (cp[r] & ~0xffffffffull) == tag;
-      if (p == PAR_ROOT) {
+      fail = fail || s == SHAPE_FAIL;
+      if (s == SHAPE_ROOT) {
         atomicAdd(&a.plan->nroot, 1u);
         const u32x4 r0 = a.c_rec[g[r]];
         a.plan->root_t = (uint64_t)r0[0] | ((uint64_t)r0[1] << 32);
-      } else if (p < 0 || !((uint64_t)p == start || (plinked && (pp[r] >= 0 || pp[r] == PAR_ROOT)))) {
-        fail = true;  // dangling: the chain through g is broken (only the start node can get here)
-      } else if (cp[r] != claim_word(a.gen, g[r])) {
-        fail = true;  // branch: another node holds the claim on the same parent
       }
     }
   }
@@ -517,14 +533,7 @@ __device__ __forceinline__ uint32_t block_rank_rounds(const bool* f, uint32_t* w
 constexpr int FIN_R = SRD_FIN_R;
 constexpr uint32_t WSLOW = 256;  // per-wave slow-entry queue (LDS) of chain_finalize_kernel
 
-// one chain entry's inputs (finalize_core's, loaded level by level)
-struct FinIn {
-  uint64_t mo, p;
-  uint32_t crc_st, fl, sxv;   // record: r1[0], r1[3], r1[1]
-  uint32_t pfl, psuf;         // parent record: r1[3], r1[2] (pfl = 3 << F_SUF_SHIFT: no parent record)
-  u32x4 t0, t1;               // per-tile values of the start tile k0 and the metadata tile k1
-};
-// the tables finalize_in reads, in LDS
+// the tables finalize_in reads, in LDS (srd_fin.h's table members)
 struct FinLds {
   uint32_t tab[1024];         // CRC slice-by-4
   uint32_t m16k[1024];        // v -> v * x^16384
@@ -533,103 +542,126 @@ struct FinLds {
   uint32_t winit[64], zero_crc[64];
   uint32_t invpow[4097];
 };
-
-__device__ __forceinline__ uint32_t mul16k_lds(const uint32_t* m16k, uint32_t v) {
-  return m16k[v & 0xff] ^ m16k[256 + ((v >> 8) & 0xff)] ^ m16k[512 + ((v >> 16) & 0xff)] ^ m16k[768 + (v >> 24)];
+// Thread ti's words of g_tabs for FinLds, through registers: loaded (store =
+// false) at the kernel's start -- the loads overlap the plan's dependent ones:
+// one round trip instead of a load -> store loop after the plan --, stored
+// once the block is past its early exits.
+constexpr int FIN_LDS_WORDS = 13;
+__device__ __forceinline__ void fin_lds_words(FinLds& lt, uint32_t ti, uint32_t (&r)[FIN_LDS_WORDS], bool store) {
+  static_assert(CHAIN_THREADS == 1024, "one word of each 1024-word table per thread");
+  int i = 0;
+  auto word = [&](uint32_t& dst, const uint32_t& src, bool mine = true) {
+    if (!store) r[i] = src;
+    else if (mine) dst = r[i];
+    i++;
+  };
+  word(lt.tab[ti], (&g_tabs.tab[0][0])[ti]);
+  word(lt.m16k[ti], (&g_tabs.m16k[0][0])[ti]);
+  word(lt.m32k[ti], (&g_tabs.m32k[0][0])[ti]);
+#pragma unroll
+  for (int j = 0; j < 3; j++) word(lt.mtk[1024 * j + ti], (&g_tabs.mtk[0][0][0])[1024 * j + ti]);
+#pragma unroll
+  for (int j = 0; j < 4; j++) word(lt.invpow[1024 * j + ti], g_tabs.invpow[1024 * j + ti]);
+  word(lt.invpow[4096], g_tabs.invpow[4096], ti == 0);
+  word(lt.winit[ti & 63], g_tabs.winit[ti & 63], ti < 64);
+  word(lt.zero_crc[ti & 63], g_tabs.zero_crc[ti & 63], ti < 64);
 }
 
-// crc_raw of bytes [floor64(m), m) (tail_crc_line) with the CRC table in LDS
-__device__ __forceinline__ uint32_t tail_crc_lds(const uint8_t* file, uint64_t m, const uint32_t* tab) {
-  return tail_crc_line(file, m, [tab](int t, uint32_t b) { return tab[256 * t + b]; });
-}
+// ---- chain_finalize_kernel's entry pass: FIN_R entries per lane per pass,
+// their loads issued level by level (level 1: the record at the slot; level
+// 2: the parent's record words and the tile values; then the stores while
+// those fly).  The two callers differ in how a lane finds its slot and chain
+// position and in where the parent's words come from; the rest is here. ----
 
-// finalize_core (srd_kernels.hip) for a candidate chain entry from its
-// preloaded inputs: the same outputs, bit for bit; true = slow_one needed
-__device__ __forceinline__ bool finalize_in(const FinArgs& a, uint64_t c, const FinIn& e, const FinLds& t) {
-  const uint32_t* m16k = t.m16k;
-  const uint64_t mo = e.mo, p = e.p;
-  const uint32_t fl = e.fl;
-  const bool tomb = fl & F_TOMB;
-  const uint64_t start = tomb ? p : p + prepad64(p);
-  const uint64_t k0 = start / TILE, k1 = mo / TILE;
-  uint32_t suf = 0, sxm = 0, tail = 0, pieces = 0;
-  if (fl & F_SXM) {
-    sxm = (fl & F_SXM_LO) ? mul16k_lds(m16k, e.sxv) ^ e.t1[2] : e.sxv;
-    pieces |= 2;
-  }
-  if (fl & F_TAIL) pieces |= 4;
-  const uint32_t kind = (e.pfl >> F_SUF_SHIFT) & 3;
-  if (kind == 0) { suf = (e.pfl & F_SUF_LO) ? mul16k_lds(m16k, e.psuf) ^ e.t0[2] : e.psuf; pieces |= 1; }
-  else if (kind == 1) { suf = mul16k_lds(m16k, e.t0[0]) ^ e.t0[2]; pieces |= 1; }
-  else if (kind == 2) { suf = mul16k_lds(m16k, e.t0[1]) ^ e.t0[2]; pieces |= 1; }
-  if (!(pieces & 1)) {  // the start line's suffix from the per-tile values (line 0, 1 or 32)
-    const uint32_t j = (uint32_t)((start % TILE) / 64);
-    if (j == 0) { suf = mul16k_lds(m16k, e.t0[0]) ^ e.t0[2]; pieces |= 1; }
-    else if (j == 1) { suf = mul16k_lds(m16k, e.t0[1]) ^ e.t0[2]; pieces |= 1; }
-    else if (j == 32) { suf = e.t0[2]; pieces |= 1; }
-  }
-  if (!(pieces & 2)) {
-    const uint32_t j = (uint32_t)((mo % TILE) / 64);
-    if (j == 0) { sxm = mul16k_lds(m16k, e.t1[0]) ^ e.t1[2]; pieces |= 2; }
-    else if (j == 1) { sxm = mul16k_lds(m16k, e.t1[1]) ^ e.t1[2]; pieces |= 2; }
-    else if (j == 32) { sxm = e.t1[2]; pieces |= 2; }
-  }
-  const uint64_t len = mo - start;
-  GST(a.o_start[c], start);  // o_mo / o_kh / o_prev / o_crc_st: stored by the caller
-  GST(a.o_len[c], len);
-  if (a.no_crc) { a.o_crc[c] = 0; a.o_ok[c] = 0; return false; }
-  uint32_t crc;
-  if (tomb) {
-    crc = 0xD202EF8Du;  // CRC32(b"\0"): the tombstone byte is 0 by the rule
-  } else {
-    if (!(pieces & 4)) tail = tail_crc_lds(a.file, mo, t.tab);
-    const bool need_long = len >= 64;
-    const bool many_tiles = need_long && k1 > k0 + 1 + LONG_TILES;
-    if (need_long && !((pieces & 1) && (pieces & 2) && !many_tiles)) {
-      a.o_pieces[c] = pieces;
-      a.o_suf[c] = suf;
-      a.o_sxm[c] = sxm;
-      a.o_tail[c] = tail;
-      return true;
-    }
-    if (!need_long) {
-      crc = tail ^ t.zero_crc[len];
-    } else {  // crc_from_pieces
-      uint32_t acc = suf ^ t.winit[(start % TILE) / 64], y;
-      if (k0 == k1) {
-        y = acc ^ sxm;
-      } else {
-        // the whole tiles 4 at a time (their values loaded together): acc =
-        // acc * X^r ^ T_0 X^(r-1) ^ ... ^ T_(r-1) for the group's r <= 4
-        // tiles (X = x^32768, tile_T(k) = mul16k(T_lo) ^ SX_32), so the
-        // dependent chain is one table multiply per 4 tiles, not per tile
-        // (the same 32 lookups per 4 tiles; C3's 2-16-tile entries)
-        const u32x4* t4 = (const u32x4*)a.tile;
-        for (uint64_t kb = k0 + 1; kb < k1; kb += 4) {
-          u32x4 tv[4];
+// level 1: core flag, parent and the record itself, all at slot gi (in: the
+// lane has a record; idle lanes load a valid slot and stay off).  own_suf =
+// the record's suf word: its child's psuf
+__device__ __forceinline__ bool fin_load_record(const ShapeArgs& a, const FinArgs& f, uint64_t gi, bool in, FinIn& e,
+                                                uint64_t& kh, int64_t& par, uint32_t& own_suf) {
+  const bool fl = in && a.flag[gi];
+  par = a.d_par[gi];
+  e.mo = f.c_m[gi];
+  const u32x4 r0 = f.c_rec[gi], r1 = f.c_rec1[gi];
+  e.p = (uint64_t)r0[0] | ((uint64_t)r0[1] << 32);
+  kh = (uint64_t)r1[0] | ((uint64_t)r1[1] << 32);
+  e.crc_st = r0[3];
+  e.sxv = r1[2];
+  e.fl = r0[2];
+  own_suf = r1[3];
+  return fl;
+}
+// the wave's ranks of the core entries of the pass (round r after rounds < r); returns their count
+__device__ __forceinline__ uint32_t fin_rank(const bool (&fl)[FIN_R], uint64_t lt_mask, uint32_t (&rank)[FIN_R]) {
+  uint32_t tot = 0;
 #pragma unroll
-          for (int q = 0; q < 4; q++) tv[q] = t4[kb + q < k1 ? kb + q : k1];
-          const uint32_t r = (uint32_t)min<uint64_t>(k1 - kb, 4);
-          uint32_t T[4];
-#pragma unroll
-          for (int q = 0; q < 4; q++) T[q] = mul16k_lds(m16k, tv[q][0]) ^ tv[q][2];
-          // X^j tables: j = 1 m32k, j = 2..4 mtk[j - 2]
-          auto xt = [&](uint32_t j) -> const uint32_t* { return j == 1 ? t.m32k : t.mtk + 1024 * (j - 2); };
-          uint32_t v = mul16k_lds(xt(r), acc) ^ T[r - 1];
-          if (r >= 2) v ^= mul16k_lds(t.m32k, T[r - 2]);
-          if (r >= 3) v ^= mul16k_lds(t.mtk, T[r - 3]);
-          if (r >= 4) v ^= mul16k_lds(t.mtk + 1024, T[0]);
-          acc = v;
-        }
-        y = mul16k_lds(t.m32k, acc) ^ (mul16k_lds(m16k, e.t1[0]) ^ e.t1[2]) ^ sxm;
-      }
-      crc = ~(mulp(t.invpow[(k1 + 1) * TILE - mo], y) ^ tail);
-    }
+  for (int r = 0; r < FIN_R; r++) {
+    const uint64_t b = __ballot(fl[r]);
+    rank[r] = tot + (uint32_t)__popcll(b & lt_mask);
+    tot += (uint32_t)__popcll(b);
   }
-  GST(a.o_crc[c], crc);
-  GST(a.o_ok[c], (uint8_t)(crc == e.crc_st));
-  if (crc != e.crc_st) atomicAdd(a.n_bad, 1ull);
-  return false;
+  return tot;
+}
+// level 2: the values of the start tile k0 and the metadata tile k1.  k0 is
+// resident: start >= p >= the span's lower tail in span mode.  Idle lanes
+// read the last tile's values (resident in span mode too)
+__device__ __forceinline__ void fin_load_tiles(const FinArgs& f, bool fl, FinIn& e) {
+  const u32x4* t4 = (const u32x4*)f.tile;
+  const uint64_t mo = fl ? e.mo : f.flen - 1;
+  const uint64_t st0 = fl ? fin_start(e.fl, e.p) : mo;
+  e.t0 = t4[st0 / TILE];
+  e.t1 = t4[mo / TILE];
+}
+// Entries whose CRC needs a wave go to the call's slow list (idx_dedup's
+// blocks run them, one wave each), gathered in the wave's LDS queue: one list
+// claim per wave and WSLOW entries.  The queue holds chain positions relative
+// to run0, the wave's first.
+struct SlowQueue {
+  uint32_t* q;      // LDS[WSLOW], this wave's
+  uint64_t run0;
+  uint32_t n;       // wave-uniform: entries queued
+  __device__ __forceinline__ void flush(const FinArgs& f) {
+    if (!n) return;
+    const uint32_t lane = threadIdx.x & 63;
+    wave_lds_sync();
+    unsigned long long sbase = 0;
+    if (lane == 0) sbase = atomicAdd(f.n_slow, (unsigned long long)n);
+    sbase = __shfl(sbase, 0);
+    for (uint32_t i = lane; i < n; i += 64) f.slow_list[sbase + i] = run0 + q[i];
+    wave_lds_sync();
+    n = 0;
+  }
+  // (every lane of the wave calls it; slow: this lane's entry c goes to the list)
+  __device__ __forceinline__ void push(const FinArgs& f, bool slow, uint64_t c, uint64_t lt_mask) {
+    const uint64_t sb = __ballot(slow);
+    const uint32_t k = (uint32_t)__popcll(sb);
+    if (!k) return;
+    if (n + k > WSLOW) flush(f);
+    if (slow) q[n + __popcll(sb & lt_mask)] = (uint32_t)(c - run0);
+    n += k;
+  }
+};
+// the pass's outputs for chain positions run + rank[r]: the record's own
+// words and the index histogram while the level-2 loads fly, then the rule
+__device__ __forceinline__ void fin_emit(const FinArgs& f, const FinLds& lt, uint32_t* hist, uint32_t log2_nbk,
+                                         uint64_t run, uint64_t lt_mask, const bool (&fl)[FIN_R],
+                                         const uint32_t (&rank)[FIN_R], const FinIn (&e)[FIN_R],
+                                         const uint64_t (&kh)[FIN_R], SlowQueue& sq) {
+#pragma unroll
+  for (int r = 0; r < FIN_R; r++) {
+    if (!fl[r]) continue;
+    const uint64_t c = run + rank[r];
+    GST(f.o_mo[c], e[r].mo);
+    GST(f.o_kh[c], kh[r]);
+    GST(f.o_packed[c], ((kh[r] >> 48) << 48) | (e[r].mo & 0xFFFFFFFFFFFFull));  // key_indexer.rs:79-85
+    GST(f.o_prev[c], e[r].p);
+    GST(f.o_crc_st[c], e[r].crc_st);
+    atomicAdd(&hist[idx_bucket(kh[r], log2_nbk)], 1u);
+  }
+#pragma unroll
+  for (int r = 0; r < FIN_R; r++) {
+    const uint64_t c = run + rank[r];
+    sq.push(f, fl[r] && finalize_in<true>(f, c, e[r], lt), c, lt_mask);
+  }
 }
 
 // ---- the fused shape check (FUSED chain_finalize_kernel, round 0) ----
@@ -734,24 +766,10 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_finalize_kernel(ShapeArgs
   __shared__ uint32_t s_pre[BW_MAX + 1];
   __shared__ uint32_t wslow[CHAIN_WAVES][WSLOW];
   __shared__ FinLds lt;
-  uint32_t* const tab = lt.tab;
   extern __shared__ uint32_t hist[];
-  // the LDS tables' words first, into registers: their loads overlap the
-  // plan's dependent ones below (one round trip instead of a load -> store
-  // loop after the plan)
-  static_assert(CHAIN_THREADS == 1024, "one word of each 1024-word table per thread");
   GLUE_STAMP(0);
-  const uint32_t ti = threadIdx.x;
-  const uint32_t r_tab = g_tabs.tab[ti >> 8][ti & 255],
-                 r_m16k = (&g_tabs.m16k[0][0])[ti], r_m32k = (&g_tabs.m32k[0][0])[ti];
-  uint32_t r_mtk[3];
-#pragma unroll
-  for (int j = 0; j < 3; j++) r_mtk[j] = (&g_tabs.mtk[j][0][0])[ti];
-  uint32_t r_inv[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) r_inv[j] = g_tabs.invpow[ti + 1024 * j];
-  const uint32_t r_inv_last = g_tabs.invpow[4096];
-  const uint32_t r_winit = g_tabs.winit[ti & 63], r_zc = g_tabs.zero_crc[ti & 63];
+  uint32_t ltw[FIN_LDS_WORDS];
+  fin_lds_words(lt, threadIdx.x, ltw, false);  // (first: the loads)
   const uint64_t K = a.Kp[0];
   const bool incomplete = dense_incomplete(a);
   uint64_t before = 0, total = 0;
@@ -870,24 +888,20 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_finalize_kernel(ShapeArgs
 #pragma unroll
           for (int r = 0; r < CR; r++) {
             if (!in[r]) break;
-            const int64_t p = par[r];
-            const bool linked = (cg[r] & ~0xffffffffull) == tag;
-            // g == the start node: the last record, at the start tail's metadata
-            const bool is_st = s1 && g[r] == s1 - 1 && top >= 21 && a.c_m[g[r]] == top - 20;
-            const bool core = is_st || (linked && (p >= 0 || p == PAR_ROOT));  // is_core(g)
-            GST(a.flag[g[r]], (uint8_t)core);
-            if (!core) continue;
+            // the start node: the last record, at the start tail's metadata
+            // (c_m is read for that slot only)
+            const Shape s = shape_test(
+                a.gen, g[r], par[r], pp[r], cp[r],
+                [&](bool parent) { return ((parent ? cp[r] : cg[r]) & ~0xffffffffull) == tag; },
+                [&](uint64_t node) { return top >= 21 && node == s1 - 1 && a.c_m[node] == top - 20; });
+            GST(a.flag[g[r]], (uint8_t)(s != SHAPE_LEAF));
+            if (s == SHAPE_LEAF) continue;
             cnt++;
-            const bool plinked = (cp[r] & ~0xffffffffull) == tag;
-            if (p == PAR_ROOT) {
+            fail = fail || s == SHAPE_FAIL;
+            if (s == SHAPE_ROOT) {
               nr++;
               const u32x4 r0 = a.c_rec[g[r]];
               s_root_t = (uint64_t)r0[0] | ((uint64_t)r0[1] << 32);  // (any one: nroot != 1 fails the call)
-            } else if (p < 0 || !(((uint64_t)p == s1 - 1 && a.c_m[p] == top - 20) ||
-                                  (plinked && (pp[r] >= 0 || pp[r] == PAR_ROOT)))) {
-              fail = true;  // dangling (a parent that is the start node is core: never here in practice)
-            } else if (cp[r] != claim_word(a.gen, g[r])) {
-              fail = true;  // branch
             }
           }
         }
@@ -904,18 +918,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_finalize_kernel(ShapeArgs
       // the LDS tables and the bucket counts now: wave 0's look-back below
       // overlaps the other waves' stores (one barrier for both)
       for (uint32_t k = threadIdx.x; k < nbk; k += blockDim.x) hist[k] = 0;
-      tab[ti] = r_tab;
-      lt.m16k[ti] = r_m16k;
-      lt.m32k[ti] = r_m32k;
-#pragma unroll
-      for (int j = 0; j < 3; j++) lt.mtk[1024 * j + ti] = r_mtk[j];
-#pragma unroll
-      for (int j = 0; j < 4; j++) lt.invpow[ti + 1024 * j] = r_inv[j];
-      if (ti == 0) lt.invpow[4096] = r_inv_last;
-      if (ti < 64) {
-        lt.winit[ti] = r_winit;
-        lt.zero_crc[ti] = r_zc;
-      }
+      fin_lds_words(lt, threadIdx.x, ltw, true);
       uint32_t btot = 0;
       for (uint32_t v = 0; v < a.wpb; v++) btot += s_vcnt[v];
       const uint32_t ltag = lb_tag(a.gen);
@@ -956,18 +959,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_finalize_kernel(ShapeArgs
   }
   if (!FUSED || troot) {  // (FUSED: stored beside the look-back above)
     for (uint32_t k = threadIdx.x; k < nbk; k += blockDim.x) hist[k] = 0;
-    tab[ti] = r_tab;
-    lt.m16k[ti] = r_m16k;
-    lt.m32k[ti] = r_m32k;
-#pragma unroll
-    for (int j = 0; j < 3; j++) lt.mtk[1024 * j + ti] = r_mtk[j];
-#pragma unroll
-    for (int j = 0; j < 4; j++) lt.invpow[ti + 1024 * j] = r_inv[j];
-    if (ti == 0) lt.invpow[4096] = r_inv_last;
-    if (ti < 64) {
-      lt.winit[ti] = r_winit;
-      lt.zero_crc[ti] = r_zc;
-    }
+    fin_lds_words(lt, threadIdx.x, ltw, true);
     __syncthreads();
   }
   GLUE_STAMP(3);
@@ -979,253 +971,124 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_finalize_kernel(ShapeArgs
   const bool root_block = FUSED && !troot ? root_t != 0 : blockIdx.x == 0;
   if (root_block && a.coff && threadIdx.x == 0) {
     uint64_t kh;
-    root_slow = finalize_core(f, 0, NO_REC, -1, root_t, &kh);
+    root_slow = finalize_core<true>(f, 0, NO_REC, -1, root_t, &kh, lt);
     atomicAdd(&hist[idx_bucket(kh, log2_nbk)], 1u);
   }
   uint64_t bend = a.coff + before;  // the end of this block's chain positions
-  if (FUSED && !troot) {
-    // the same scan waves per chain wave as the check above; a scan wave's
-    // chain positions start at this block's prefix + the core records of the
-    // block's earlier scan waves
+  if (!troot) {
     const uint32_t wi = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint64_t lt_mask = (1ull << lane) - 1;
-    uint32_t btot = 0;
-    for (uint32_t v = 0; v < a.wpb; v++) btot += s_vcnt[v];
-    bend += btot;
-    auto wave_sync = [&]() {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    const u32x4* t4 = (const u32x4*)f.tile;
-    for (uint32_t v = wi; v < a.wpb; v += CHAIN_WAVES) {
-      const uint64_t w = (uint64_t)blockIdx.x * a.wpb + v;
-      const uint32_t n = w < a.n_waves ? (uint32_t)min(a.wave_total[w] & ~(1ull << 63), a.wcap) : 0u;
-      const uint64_t gb = w * a.wcap;
-      uint32_t voff = 0;
-      for (uint32_t u = 0; u < v; u++) voff += s_vcnt[u];
-      uint64_t run = a.coff + before + voff;  // this scan wave's next chain position
-      const uint64_t run0 = run;
-      uint32_t nsq = 0;  // wave-uniform: entries in the wave's slow queue
-      auto flush_slow = [&]() {
-        if (!nsq) return;
-        wave_sync();
-        unsigned long long sbase = 0;
-        if (lane == 0) sbase = atomicAdd(f.n_slow, (unsigned long long)nsq);
-        sbase = __shfl(sbase, 0);
-        for (uint32_t q = lane; q < nsq; q += 64) f.slow_list[sbase + q] = run0 + wslow[wi][q];
-        wave_sync();
-      };
-      uint32_t c_fl = 3u << F_SUF_SHIFT, c_suf = 0;  // the previous pass's lane-63 record words
-      for (uint32_t base = 0; base < n; base += 64 * FIN_R) {
+    SlowQueue sq = {wslow[wi], 0, 0};
+    if constexpr (FUSED) {
+      // the same scan waves per chain wave as the check above; a scan wave's
+      // chain positions start at this block's prefix + the core records of the
+      // block's earlier scan waves
+      uint32_t btot = 0;
+      for (uint32_t v = 0; v < a.wpb; v++) btot += s_vcnt[v];
+      bend += btot;
+      for (uint32_t v = wi; v < a.wpb; v += CHAIN_WAVES) {
+        const uint64_t w = (uint64_t)blockIdx.x * a.wpb + v;
+        const uint32_t n = w < a.n_waves ? (uint32_t)min(a.wave_total[w] & ~(1ull << 63), a.wcap) : 0u;
+        const uint64_t gb = w * a.wcap;
+        uint32_t voff = 0;
+        for (uint32_t u = 0; u < v; u++) voff += s_vcnt[u];
+        uint64_t run = a.coff + before + voff;  // this scan wave's next chain position
+        sq.run0 = run;
+        uint32_t c_fl = F_NO_PARENT, c_suf = 0;  // the previous pass's lane-63 record words
+        for (uint32_t base = 0; base < n; base += 64 * FIN_R) {
+          bool fl[FIN_R];
+          uint64_t gi[FIN_R], kh[FIN_R];
+          int64_t par[FIN_R];
+          uint32_t psuf[FIN_R], rank[FIN_R];
+          FinIn e[FIN_R];
+#pragma unroll
+          for (int r = 0; r < FIN_R; r++) {
+            const uint32_t i = base + (uint32_t)r * 64 + lane;
+            gi[r] = gb + (i < n ? i : 0u);
+            fl[r] = fin_load_record(a, f, gi[r], i < n, e[r], kh[r], par[r], psuf[r]);
+          }
+          const uint32_t tot = fin_rank(fl, lt_mask, rank);
+          // level 2: the parent's record words -- the previous record's (the
+          // neighbour lane) when it is the parent, else a load.  A root-linked
+          // candidate has no parent record (start 0)
+          bool any = false, need[FIN_R];
+#pragma unroll
+          for (int r = 0; r < FIN_R; r++) {
+            const uint32_t i = base + (uint32_t)r * 64 + lane;
+            const uint32_t l0f = r ? (uint32_t)__builtin_amdgcn_readlane(e[r - 1].fl, 63) : c_fl;
+            const uint32_t l0s = r ? (uint32_t)__builtin_amdgcn_readlane(psuf[r - 1], 63) : c_suf;
+            const uint32_t nf = prev_lane(e[r].fl, l0f), ns = prev_lane(psuf[r], l0s);
+            need[r] = fl[r] && par[r] >= 0 && !(i > 0 && (uint64_t)par[r] == gi[r] - 1);
+            any = any || need[r];
+            e[r].pfl = par[r] >= 0 ? nf : F_NO_PARENT;
+            e[r].psuf = ns;
+            fin_load_tiles(f, fl[r], e[r]);
+          }
+          if (__ballot(any)) {  // (uniform)
+#pragma unroll
+            for (int r = 0; r < FIN_R; r++)
+              if (need[r]) {
+                e[r].pfl = f.c_rec[par[r]][2];
+                e[r].psuf = f.c_rec1[par[r]][3];
+              }
+          }
+          c_fl = (uint32_t)__builtin_amdgcn_readlane(e[FIN_R - 1].fl, 63);
+          c_suf = (uint32_t)__builtin_amdgcn_readlane(psuf[FIN_R - 1], 63);
+          fin_emit(f, lt, hist, log2_nbk, run, lt_mask, fl, rank, e, kh, sq);
+          run += tot;
+        }
+        sq.flush(f);
+      }
+    } else {
+      const uint32_t n = block_waves(a, s_pre);
+      // wave chunks as in check_kernel: wave wi ranks its records from its
+      // chunk's offset (the per-chunk core counts) with ballots -- the waves
+      // never wait for each other inside the loop
+      uint32_t woff, btot;
+      {
+        const uint32_t v = lane < CHAIN_WAVES ? a.wpart[blockIdx.x * CHAIN_WAVES + lane] : 0u;
+        uint32_t x = lane < wi ? v : 0u, y = v;
+#pragma unroll
+        for (int o = 32; o; o >>= 1) {
+          x += __shfl_xor(x, o);
+          y += __shfl_xor(y, o);
+        }
+        woff = x;
+        btot = y;
+      }
+      bend += btot;
+      uint64_t run = a.coff + before + woff;  // this wave's next chain position
+      sq.run0 = run;
+      const uint32_t chunk = (n + CHAIN_WAVES - 1) / CHAIN_WAVES;
+      const uint32_t c0 = min(n, wi * chunk), c1 = min(n, c0 + chunk);
+      for (uint32_t base = c0; base < c1; base += 64 * FIN_R) {
         bool fl[FIN_R];
         uint64_t gi[FIN_R], kh[FIN_R];
         int64_t par[FIN_R];
-        uint32_t psuf[FIN_R];
+        uint32_t own_suf, rank[FIN_R];
         FinIn e[FIN_R];
-        // level 1: core flag, parent and the record itself, all at the slot
 #pragma unroll
-        for (int r = 0; r < FIN_R; r++) {
+        for (int r = 0; r < FIN_R; r++) {  // (idle lanes: the chunk's first record)
           const uint32_t i = base + (uint32_t)r * 64 + lane;
-          gi[r] = gb + (i < n ? i : 0u);
-          fl[r] = i < n && a.flag[gi[r]];
-          par[r] = a.d_par[gi[r]];
-          e[r].mo = f.c_m[gi[r]];
-          const u32x4 r0 = f.c_rec[gi[r]], r1 = f.c_rec1[gi[r]];
-          e[r].p = (uint64_t)r0[0] | ((uint64_t)r0[1] << 32);
-          kh[r] = (uint64_t)r1[0] | ((uint64_t)r1[1] << 32);
-          e[r].crc_st = r0[3];
-          e[r].sxv = r1[2];
-          e[r].fl = r0[2];
-          psuf[r] = r1[3];
+          gi[r] = slot_of(a, s_pre, i < c1 ? i : c0);
+          fl[r] = fin_load_record(a, f, gi[r], i < c1, e[r], kh[r], par[r], own_suf);
         }
-        uint32_t rank[FIN_R], tot = 0;
+        const uint32_t tot = fin_rank(fl, lt_mask, rank);
+        // level 2: the parent's record, by a load.  A root-linked candidate
+        // (par == PAR_ROOT) has no parent record: its suffix comes from the
+        // per-tile values (start 0)
 #pragma unroll
         for (int r = 0; r < FIN_R; r++) {
-          const uint64_t b = __ballot(fl[r]);
-          rank[r] = tot + (uint32_t)__popcll(b & lt_mask);
-          tot += (uint32_t)__popcll(b);
+          const uint64_t pg = fl[r] && par[r] >= 0 ? (uint64_t)par[r] : gi[r];
+          e[r].pfl = par[r] >= 0 ? f.c_rec[pg][2] : F_NO_PARENT;
+          e[r].psuf = f.c_rec1[pg][3];
+          fin_load_tiles(f, fl[r], e[r]);
         }
-        // level 2: the parent's record words -- the previous record's (the
-        // neighbour lane) when it is the parent, else a load -- and the tile
-        // values.  A root-linked candidate has no parent record (start 0)
-        bool any = false, need[FIN_R];
-#pragma unroll
-        for (int r = 0; r < FIN_R; r++) {
-          const uint32_t i = base + (uint32_t)r * 64 + lane;
-          const uint32_t l0f = r ? (uint32_t)__builtin_amdgcn_readlane(e[r - 1].fl, 63) : c_fl;
-          const uint32_t l0s = r ? (uint32_t)__builtin_amdgcn_readlane(psuf[r - 1], 63) : c_suf;
-          const uint32_t nf = prev_lane(e[r].fl, l0f), ns = prev_lane(psuf[r], l0s);
-          need[r] = fl[r] && par[r] >= 0 && !(i > 0 && (uint64_t)par[r] == gi[r] - 1);
-          any = any || need[r];
-          e[r].pfl = par[r] >= 0 ? nf : (3u << F_SUF_SHIFT);
-          e[r].psuf = ns;
-          // idle lanes read the last tile's values (resident in span mode too)
-          const uint64_t mo = fl[r] ? e[r].mo : f.flen - 1;
-          const uint64_t st0 = !fl[r] ? mo : (e[r].fl & F_TOMB) ? e[r].p : e[r].p + prepad64(e[r].p);
-          e[r].t0 = t4[st0 / TILE];
-          e[r].t1 = t4[mo / TILE];
-        }
-        if (__ballot(any)) {  // (uniform)
-#pragma unroll
-          for (int r = 0; r < FIN_R; r++)
-            if (need[r]) {
-              e[r].pfl = f.c_rec[par[r]][2];
-              e[r].psuf = f.c_rec1[par[r]][3];
-            }
-        }
-        c_fl = (uint32_t)__builtin_amdgcn_readlane(e[FIN_R - 1].fl, 63);
-        c_suf = (uint32_t)__builtin_amdgcn_readlane(psuf[FIN_R - 1], 63);
-        // the record's own outputs and the index histogram while those loads fly
-#pragma unroll
-        for (int r = 0; r < FIN_R; r++) {
-          if (!fl[r]) continue;
-          const uint64_t c = run + rank[r];
-          GST(f.o_mo[c], e[r].mo);
-          GST(f.o_kh[c], kh[r]);
-          GST(f.o_packed[c], ((kh[r] >> 48) << 48) | (e[r].mo & 0xFFFFFFFFFFFFull));  // key_indexer.rs:79-85
-          GST(f.o_prev[c], e[r].p);
-          GST(f.o_crc_st[c], e[r].crc_st);
-          atomicAdd(&hist[idx_bucket(kh[r], log2_nbk)], 1u);
-        }
-#pragma unroll
-        for (int r = 0; r < FIN_R; r++) {
-          const uint64_t c = run + rank[r];
-          const bool slow = fl[r] && finalize_in(f, c, e[r], lt);
-          const uint64_t sb = __ballot(slow);
-          const uint32_t k = (uint32_t)__popcll(sb);
-          if (k) {
-            if (nsq + k > WSLOW) {
-              flush_slow();
-              nsq = 0;
-            }
-            if (slow) wslow[wi][nsq + __popcll(sb & lt_mask)] = (uint32_t)(c - run0);
-            nsq += k;
-          }
-        }
+        fin_emit(f, lt, hist, log2_nbk, run, lt_mask, fl, rank, e, kh, sq);
         run += tot;
       }
-      flush_slow();
+      sq.flush(f);
     }
-  } else if (!troot) {
-    const uint32_t n = block_waves(a, s_pre);
-    // wave chunks as in check_kernel: wave wi ranks its records from its
-    // chunk's offset (the per-chunk core counts) with ballots -- the waves
-    // never wait for each other inside the loop
-    const uint32_t wi = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint64_t lt_mask = (1ull << lane) - 1;
-    uint32_t woff, btot;
-    {
-      const uint32_t v = lane < CHAIN_WAVES ? a.wpart[blockIdx.x * CHAIN_WAVES + lane] : 0u;
-      uint32_t x = lane < wi ? v : 0u, y = v;
-#pragma unroll
-      for (int o = 32; o; o >>= 1) {
-        x += __shfl_xor(x, o);
-        y += __shfl_xor(y, o);
-      }
-      woff = x;
-      btot = y;
-    }
-    bend += btot;
-    uint64_t run = a.coff + before + woff;  // this wave's next chain position
-    const uint64_t run0 = run;
-    uint32_t nsq = 0;  // wave-uniform: entries in the wave's slow queue
-    // (the queue passes values between lanes through LDS: wavefront fences
-    // and a wave barrier order the writers' stores before the reads here and
-    // the reads before the slots' reuse, as scan_kernel's window does)
-    auto wave_sync = [&]() {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    auto flush_slow = [&]() {
-      if (!nsq) return;
-      wave_sync();
-      unsigned long long sbase = 0;
-      if (lane == 0) sbase = atomicAdd(f.n_slow, (unsigned long long)nsq);
-      sbase = __shfl(sbase, 0);
-      for (uint32_t q = lane; q < nsq; q += 64) f.slow_list[sbase + q] = run0 + wslow[wi][q];
-      wave_sync();
-    };
-    const uint32_t chunk = (n + CHAIN_WAVES - 1) / CHAIN_WAVES;
-    const uint32_t c0 = min(n, wi * chunk), c1 = min(n, c0 + chunk);
-    const u32x4* t4 = (const u32x4*)f.tile;
-    for (uint32_t base = c0; base < c1; base += 64 * FIN_R) {
-      bool fl[FIN_R];
-      uint64_t gi[FIN_R], kh[FIN_R];
-      int64_t par[FIN_R];
-      FinIn e[FIN_R];
-      // level 1: core flag, parent and the record itself, all at the record's
-      // slot (idle lanes: the chunk's first record)
-#pragma unroll
-      for (int r = 0; r < FIN_R; r++) {
-        const uint32_t i = base + (uint32_t)r * 64 + lane;
-        gi[r] = slot_of(a, s_pre, i < c1 ? i : c0);
-        fl[r] = i < c1 && a.flag[gi[r]];
-        par[r] = a.d_par[gi[r]];
-        e[r].mo = f.c_m[gi[r]];
-        const u32x4 r0 = f.c_rec[gi[r]], r1 = f.c_rec1[gi[r]];
-        e[r].p = (uint64_t)r0[0] | ((uint64_t)r0[1] << 32);
-        kh[r] = (uint64_t)r1[0] | ((uint64_t)r1[1] << 32);
-        e[r].crc_st = r0[3];
-        e[r].sxv = r1[2];
-        e[r].fl = r0[2];
-      }
-      uint32_t rank[FIN_R], tot = 0;
-#pragma unroll
-      for (int r = 0; r < FIN_R; r++) {
-        const uint64_t b = __ballot(fl[r]);
-        rank[r] = tot + (uint32_t)__popcll(b & lt_mask);
-        tot += (uint32_t)__popcll(b);
-      }
-      // level 2: the parent's record, the tile values and table words.  k0
-      // (the entry's start tile) is resident: start >= p >= the span's lower
-      // tail in span mode.  A root-linked candidate (par == PAR_ROOT) has no
-      // parent record: its suffix comes from the per-tile values (start 0)
-#pragma unroll
-      for (int r = 0; r < FIN_R; r++) {
-        const uint64_t pg = fl[r] && par[r] >= 0 ? (uint64_t)par[r] : gi[r];
-        e[r].pfl = par[r] >= 0 ? f.c_rec[pg][2] : (3u << F_SUF_SHIFT);
-        e[r].psuf = f.c_rec1[pg][3];
-        // idle lanes read the last tile's values (resident in span mode too)
-        const uint64_t mo = fl[r] ? e[r].mo : f.flen - 1;
-        const uint64_t st0 = !fl[r] ? mo : (e[r].fl & F_TOMB) ? e[r].p : e[r].p + prepad64(e[r].p);
-        e[r].t0 = t4[st0 / TILE];
-        e[r].t1 = t4[mo / TILE];
-      }
-      // the record's own outputs and the index histogram while those loads fly
-#pragma unroll
-      for (int r = 0; r < FIN_R; r++) {
-        if (!fl[r]) continue;
-        const uint64_t c = run + rank[r];
-        GST(f.o_mo[c], e[r].mo);
-        GST(f.o_kh[c], kh[r]);
-        GST(f.o_packed[c], ((kh[r] >> 48) << 48) | (e[r].mo & 0xFFFFFFFFFFFFull));  // key_indexer.rs:79-85
-        GST(f.o_prev[c], e[r].p);
-        GST(f.o_crc_st[c], e[r].crc_st);
-        atomicAdd(&hist[idx_bucket(kh[r], log2_nbk)], 1u);
-      }
-      // entries whose CRC needs a wave go to the call's slow list (idx_dedup's
-      // blocks run them, one wave each), gathered in the wave's LDS queue:
-      // one list claim per wave and WSLOW entries
-#pragma unroll
-      for (int r = 0; r < FIN_R; r++) {
-        const uint64_t c = run + rank[r];
-        const bool slow = fl[r] && finalize_in(f, c, e[r], lt);
-        const uint64_t sb = __ballot(slow);
-        const uint32_t k = (uint32_t)__popcll(sb);
-        if (k) {
-          if (nsq + k > WSLOW) {
-            flush_slow();
-            nsq = 0;
-          }
-          if (slow) wslow[wi][nsq + __popcll(sb & lt_mask)] = (uint32_t)(c - run0);
-          nsq += k;
-        }
-      }
-      run += tot;
-    }
-    flush_slow();
   }
   if (root_slow) f.slow_list[atomicAdd(f.n_slow, 1ull)] = 0;  // (block 0, thread 0 only)
   __syncthreads();

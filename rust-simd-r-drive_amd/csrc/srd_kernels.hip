@@ -29,6 +29,7 @@
 #include "srd_crc.h"
 #include "srd_xxh3.h"
 #include "srd_part.h"
+#include "srd_fin.h"
 
 namespace srd {
 
@@ -37,18 +38,12 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
 
-constexpr int TILE = 4096;
 constexpr int SPAN_TILES = 4;
 constexpr uint64_t SPAN_BYTES = (uint64_t)TILE * SPAN_TILES;
 constexpr int64_t PAR_ROOT = -1;
 constexpr int64_t PAR_MISS = -2;
 
-// flags of a candidate record
-constexpr uint32_t F_TOMB = 1u, F_TAIL = 2u, F_SXM = 4u;
-constexpr int F_SUF_SHIFT = 3;        // 2 bits: 0 value, 1 next-tile T, 2 next-tile SX1, 3 missing
-// the recorded sxm / suf value is a lower-half partial (line < 32): true value =
-// mul16k(v) ^ SX_32 of the tile holding m (sxm) or the entry start (suf kind 0) -- see lo_fix()
-constexpr uint32_t F_SXM_LO = 32u, F_SUF_LO = 64u;
+// flags of a candidate record: srd_fin.h (F_TOMB .. F_SUF_LO), and for the
 // single-candidate record of the optimistic scan: link_record applies the
 // node test (F_NT); F_ZB = the byte at m - 1 is 0 (the tombstone rule's byte
 // when p == m - 1)
@@ -188,7 +183,6 @@ __device__ __forceinline__ uint32_t ld_u32_unaligned(const uint8_t* f, uint64_t 
   for (int k = 0; k < 4; k++) v |= (uint32_t)f[o + k] << (8 * k);
   return v;
 }
-__device__ __forceinline__ uint64_t prepad64(uint64_t o) { return (64 - (o & 63)) & 63; }
 
 // Stores of results another kernel reads (the glue's outputs, the scan's
 // records and tile values): relaxed system-scope stores (sc0 sc1), written
@@ -298,11 +292,16 @@ __device__ __forceinline__ uint32_t tab_lookup(const ScanLds& L, uint32_t s, uin
   const uint32_t addr = __builtin_amdgcn_perm(s, R, sel);
   return *(const uint32_t*)((const char*)L.tab + addr);
 }
+// Values passed between the lanes of one wave through LDS: wavefront fences
+// and a wave barrier order the writers' stores before the reads that follow,
+// and those reads before the slots' reuse.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
   return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);  // one v_bitop3_b32
-}
-__device__ __forceinline__ uint32_t mulfix(uint32_t v, const uint32_t* __restrict__ m) {
-  return m[v & 0xff] ^ m[256 + ((v >> 8) & 0xff)] ^ m[512 + ((v >> 16) & 0xff)] ^ m[768 + (v >> 24)];
 }
 // The raw CRC-32 of a lane's 64-byte line by slice-by-4 as 4 independent
 // 16-byte chains (4 dependent LDS round trips instead of 16): raw(line) = a x^384 ^ b x^256 ^ c x^128 ^ d for
@@ -422,9 +421,6 @@ __device__ __forceinline__ uint32_t lane_weight_or(uint32_t c, uint32_t lbase) {
     v[pos] = lds_ld(((x & 0x780u) | lbase) + pos * 2048);
   }
   return xor3(xor3(v[0], v[1], v[2]), xor3(v[3], v[4], v[5]), v[6] ^ v[7]);
-}
-__device__ __forceinline__ uint32_t mul16k(uint32_t v, const uint32_t* __restrict__ m) {
-  return m[v & 0xff] ^ m[256 + ((v >> 8) & 0xff)] ^ m[512 + ((v >> 16) & 0xff)] ^ m[768 + (v >> 24)];
 }
 // Half-tile suffix XOR: lanes >= 32 get XOR_{i>=l} u_i (the true SX_l);
 // lanes < 32 get XOR_{l<=i<32} u_i (true SX_l = mul16k(.) ^ SX_32).
@@ -1082,9 +1078,7 @@ void scan_kernel(ScanArgs a) {
         for (int j = 0; j < 4; j++) *(u32x4*)&win[4 + 4 * j] = u32x4{d[4 * j], d[4 * j + 1], d[4 * j + 2], d[4 * j + 3]};
         *(u32x2*)&win[20] = u32x2{n0, n1};
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       const uint32_t b = lane;
       const int r = 64 * f + (int)b - 14;  // m - B, in [-14, 4081]
       const uint32_t o = b + 2;            // m's byte offset in the window
@@ -1095,9 +1089,7 @@ void scan_kernel(ScanArgs a) {
       for (int i = 0; i < 6; i++) W[i] = win[base + i];
       const uint32_t tdw = win[(o - 1) >> 2];
       const uint32_t hxp = win[22];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       // level 2, exact: p >> 32 <= (file_len-1) >> 32 (roots: p == 0 pass too)
       const uint32_t f3 = alignb(W[4], W[3], sh);
       const uint32_t f2 = alignb(W[3], W[2], sh);
@@ -1741,7 +1733,7 @@ struct FinArgs {
   const uint64_t* c_m;
   const u32x4* c_rec;        // {p, flags, crc} (ScanArgs::c_rec)
   const u32x4* c_rec1;       // {key_hash, sxm, suf}
-  const uint32_t* tile;      // [4k..4k+2] per-tile values (tile_T / tile_SX1)
+  const uint32_t* tile;      // [4k..4k+2] per-tile values (srd_fin.h: tile_suffix)
   int no_crc;
   // device-side plan (sync-free path): when set, n_chain / root_t come from
   // device memory and a nonzero *status disables the kernel
@@ -1764,83 +1756,25 @@ struct FinArgs {
   unsigned long long* n_bad;
 };
 
-// crc_raw of bytes [floor64(m), m) (<= 63 bytes) in one round trip: the
-// 64-byte line at floor64(m) by four independent 16-byte loads (the store is
-// readable to srd_padded_size, so the whole line is), then <= 15 slice-by-4
-// word steps and <= 3 byte steps from registers.  (A word load per step made
-// every step wait for its own HBM round trip: up to 18 dependent loads per
-// entry, which set C3's finalize pass time.)  tab(t, b) = slice table t, byte b.
-template <class Tab>
-__device__ __forceinline__ uint32_t tail_crc_line(const uint8_t* file, uint64_t m, Tab tab) {
-  const uint64_t L = m & ~63ull;
-  const uint32_t r = (uint32_t)(m - L);
-  if (r == 0) return 0;
-  const u32x4* lp = (const u32x4*)(file + L);
-  const u32x4 q0 = lp[0], q1 = lp[1], q2 = lp[2], q3 = lp[3];
-  const uint32_t w[16] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3],
-                          q2[0], q2[1], q2[2], q2[3], q3[0], q3[1], q3[2], q3[3]};
-  uint32_t s = 0;
-#pragma unroll
-  for (int i = 0; i < 15; i++) {
-    if (4u * i + 4u <= r) {
-      s ^= w[i];
-      s = tab(3, s & 0xff) ^ tab(2, (s >> 8) & 0xff) ^ tab(1, (s >> 16) & 0xff) ^ tab(0, s >> 24);
-    }
-  }
-  uint32_t pw = 0;  // the partial word w[r / 4] (selects: no indexed register access)
-#pragma unroll
-  for (int i = 0; i < 16; i++) pw = (uint32_t)i == (r >> 2) ? w[i] : pw;
-  for (uint32_t b = 0; b < (r & 3u); b++) s = tab(0, (s ^ (pw >> (8 * b))) & 0xff) ^ (s >> 8);
-  return s;
-}
-__device__ __forceinline__ uint32_t tail_crc(const uint8_t* file, uint64_t m) {
-  return tail_crc_line(file, m, [](int t, uint32_t b) { return g_tabs.tab[t][b]; });
+// the flat view of g_tabs the shared rule reads (srd_fin.h)
+__device__ __forceinline__ FinTabs fin_tabs_global() {
+  return {&g_tabs.tab[0][0], &g_tabs.m16k[0][0], &g_tabs.m32k[0][0], &g_tabs.mtk[0][0][0], g_tabs.winit,
+          g_tabs.zero_crc,   g_tabs.invpow,      g_tabs.x32768};
 }
 
-// per-tile values: tile[4k] / tile[4k+1] = half-tile partials of lines 0 / 1,
-// tile[4k+2] = SX_32.  A lower-half partial v becomes the true suffix value
-// SX_j = v * x^16384 ^ SX_32.
-__device__ __forceinline__ uint32_t mul16k_g(uint32_t v) {
-  return g_tabs.m16k[0][v & 0xff] ^ g_tabs.m16k[1][(v >> 8) & 0xff] ^ g_tabs.m16k[2][(v >> 16) & 0xff] ^
-         g_tabs.m16k[3][v >> 24];
-}
-__device__ __forceinline__ uint32_t lo_fix(const uint32_t* tile, uint64_t k, uint32_t v) {
-  return mul16k_g(v) ^ tile[4 * k + 2];
-}
-__device__ __forceinline__ uint32_t tile_T(const uint32_t* tile, uint64_t k) { return lo_fix(tile, k, tile[4 * k]); }
-__device__ __forceinline__ uint32_t tile_SX1(const uint32_t* tile, uint64_t k) {
-  return lo_fix(tile, k, tile[4 * k + 1]);
-}
+// one chain entry's inputs (chain_finalize_kernel loads them level by level)
+struct FinIn {
+  uint64_t mo, p;
+  uint32_t crc_st, fl, sxv;   // record: r0[3], r0[2], r1[2]
+  uint32_t pfl, psuf;         // parent record: r0[2], r1[3] (pfl = F_NO_PARENT: no parent record)
+  u32x4 t0, t1;               // per-tile values of the start tile k0 and the metadata tile k1
+};
 
-__device__ __forceinline__ uint32_t crc_from_pieces(uint64_t s, uint64_t m, uint32_t suf, uint32_t sxm,
-                                                    uint32_t tail, const uint32_t* tile) {
-  const uint64_t len = m - s;
-  if (len < 64) return tail ^ g_tabs.zero_crc[len];
-  const uint64_t k0 = s / TILE, k1 = m / TILE;
-  const uint32_t j0 = (uint32_t)((s % TILE) / 64);
-  uint32_t acc = suf ^ g_tabs.winit[j0];
-  uint32_t y;
-  if (k0 == k1) {
-    y = acc ^ sxm;
-  } else {
-    for (uint64_t k = k0 + 1; k < k1; k++) acc = mulp(g_tabs.x32768, acc) ^ tile_T(tile, k);
-    y = mulp(g_tabs.x32768, acc) ^ tile_T(tile, k1) ^ sxm;
-  }
-  const uint64_t dd = (k1 + 1) * TILE - m;
-  return ~(mulp(g_tabs.invpow[dd], y) ^ tail);
-}
-
-// whole tiles a finalize thread combines serially (longer entries go to the
-// slow list, a wave each).  C3 glue (tools/lib_ab.py, contexts interleaved):
-// 4 -> 1.66 ms, 8 -> 1.61, 16 -> 1.57, 32 -> 1.57; C2 (entries of 2 tiles)
-// unchanged
-#ifndef SRD_LONG_TILES
-#define SRD_LONG_TILES 16
-#endif
-constexpr uint64_t LONG_TILES = SRD_LONG_TILES;
 constexpr uint64_t NO_REC = ~0ull;
 __device__ void finalize_one(const FinArgs& a, uint64_t c, uint64_t root_t);
-__device__ bool finalize_core(const FinArgs& a, uint64_t c, uint64_t gi, int64_t pgi, uint64_t root_t, uint64_t* kh_out);
+template <bool GROUPED, class T>
+__device__ bool finalize_core(const FinArgs& a, uint64_t c, uint64_t gi, int64_t pgi, uint64_t root_t, uint64_t* kh_out,
+                              const T& t);
 __global__ void finalize_kernel(FinArgs a) {
   uint64_t n = a.n_chain, root_t = 0;
   if (a.d_status) {
@@ -1865,112 +1799,81 @@ __device__ void finalize_one(const FinArgs& a, uint64_t c, uint64_t root_t) {
     if (pg >= 0) pgi = (int64_t)(a.d_status ? a.chain_g[c - 1] : a.slot[pg]);
   }
   uint64_t kh;
-  if (finalize_core(a, c, gi, pgi, root_t, &kh)) {
+  if (finalize_core<false>(a, c, gi, pgi, root_t, &kh, fin_tabs_global())) {
     const unsigned long long w = atomicAdd(a.n_slow, 1ull);
     a.slow_list[w] = c;
   }
 }
 
-// Chain entry c: its candidate record gi (NO_REC: the root entry, from
-// root_t) and its parent's record pgi (< 0: the parent is the root entry or
-// lies outside the span).  Writes every output; returns true when the CRC
-// needs slow_one (o_pieces / o_suf / o_sxm / o_tail hold its inputs then).
-__device__ bool finalize_core(const FinArgs& a, uint64_t c, uint64_t gi, int64_t pgi, uint64_t root_t,
-                              uint64_t* kh_out) {
-  uint64_t mo, kh, p, start, len;
-  uint32_t crc_st, suf = 0, sxm = 0, tail = 0, pieces = 0;
-  bool tomb;
-  if (gi == NO_REC) {
-    const uint64_t t = root_t;
-    mo = t - 20;
-    kh = ld_u64_unaligned(a.file, mo);
-    crc_st = ld_u32_unaligned(a.file, mo + 16);
-    p = 0;
-    tomb = false;  // start is 0 either way
-    start = 0;
-    suf = tile_T(a.tile, 0);
-    pieces = 1;
-  } else {
-    mo = a.c_m[gi];
-    const u32x4 r0 = a.c_rec[gi], r1 = a.c_rec1[gi];
-    p = (uint64_t)r0[0] | ((uint64_t)r0[1] << 32);
-    kh = (uint64_t)r1[0] | ((uint64_t)r1[1] << 32);
-    crc_st = r0[3];
-    const uint32_t fl = r0[2];
-    tomb = fl & F_TOMB;
-    start = tomb ? p : p + prepad64(p);
-    if (fl & F_SXM) {
-      sxm = (fl & F_SXM_LO) ? lo_fix(a.tile, mo / TILE, r1[2]) : r1[2];
-      pieces |= 2;
-    }
-    if (fl & F_TAIL) { tail = 0; pieces |= 4; }
-    if (pgi >= 0) {
-      const uint32_t pfl = a.c_rec[pgi][2], psuf = a.c_rec1[pgi][3];
-      const uint32_t kind = (pfl >> F_SUF_SHIFT) & 3;
-      const uint64_t k0 = start / TILE;  // kind 0: the parent's tile; 1, 2: the next one
-      if (kind == 0) { suf = (pfl & F_SUF_LO) ? lo_fix(a.tile, k0, psuf) : psuf; pieces |= 1; }
-      else if (kind == 1) { suf = tile_T(a.tile, k0); pieces |= 1; }
-      else if (kind == 2) { suf = tile_SX1(a.tile, k0); pieces |= 1; }
-    } else if (start == 0) {
-      suf = tile_T(a.tile, 0);
-      pieces |= 1;
-    }
-  }
-  *kh_out = kh;
-  // A piece no record holds (the root entry's metadata-line suffix, its
-  // child's start-line suffix: the root has no candidate record) comes from
-  // the per-tile values when its line is 0, 1 or 32 of the tile (C1/C2/C5:
-  // root metadata at 4096, the child's start at 4160); else slow_kernel
-  // recomputes it
-  if (!(pieces & 1)) {
-    const uint64_t k = start / TILE;
-    const uint32_t j = (uint32_t)((start % TILE) / 64);
-    if (j == 0) { suf = tile_T(a.tile, k); pieces |= 1; }
-    else if (j == 1) { suf = tile_SX1(a.tile, k); pieces |= 1; }
-    else if (j == 32) { suf = a.tile[4 * k + 2]; pieces |= 1; }
-  }
-  if (!(pieces & 2)) {
-    const uint64_t k = mo / TILE;
-    const uint32_t j = (uint32_t)((mo % TILE) / 64);
-    if (j == 0) { sxm = tile_T(a.tile, k); pieces |= 2; }
-    else if (j == 1) { sxm = tile_SX1(a.tile, k); pieces |= 2; }
-    else if (j == 32) { sxm = a.tile[4 * k + 2]; pieces |= 2; }
-  }
-  len = mo - start;
-  a.o_mo[c] = mo;
-  a.o_kh[c] = kh;
-  if (a.o_packed) a.o_packed[c] = ((kh >> 48) << 48) | (mo & 0xFFFFFFFFFFFFull);  // key_indexer.rs:79-85
-  a.o_prev[c] = p;
-  a.o_start[c] = start;
-  a.o_len[c] = len;
-  a.o_crc_st[c] = crc_st;
+// Chain entry c from its inputs e (o_mo / o_kh / o_prev / o_crc_st: stored by
+// the caller): the shared rule (srd_fin.h), then o_start, o_len and the CRC.
+// GROUPED: the whole tiles 4 per step (crc_from_pieces4; t needs m32k / mtk).
+// Returns true when the CRC needs slow_one (o_pieces / o_suf / o_sxm / o_tail
+// hold its inputs then).
+template <bool GROUPED, class T>
+__device__ __forceinline__ bool finalize_in(const FinArgs& a, uint64_t c, const FinIn& e, const T& t) {
+  const uint64_t mo = e.mo, start = fin_start(e.fl, e.p), len = mo - start;
+  const FinPieces pc = fin_pieces(e.fl, e.sxv, e.pfl, e.psuf, e.t0, e.t1, start, mo, t);
+  srd_gst(&a.o_start[c], start);  // (written through, as the glue's other outputs: srd_glue.hip)
+  srd_gst(&a.o_len[c], len);
   if (a.no_crc) { a.o_crc[c] = 0; a.o_ok[c] = 0; return false; }
-  if (tomb) {
-    const uint32_t crc = 0xD202EF8Du;  // CRC32(b"\0"): the tombstone byte is 0 by the rule
-    a.o_crc[c] = crc;
-    a.o_ok[c] = crc == crc_st;
-    if (crc != crc_st) atomicAdd(a.n_bad, 1ull);
-    return false;
+  uint32_t crc = TOMB_CRC;
+  if (!(e.fl & F_TOMB)) {
+    const uint32_t tail = (pc.pieces & 4) ? 0u : tail_crc_line<u32x4>(a.file, mo, t);  // re-read the partial last line
+    if (fin_route(len, start / TILE, mo / TILE, pc.pieces) == FIN_SLOW) {
+      a.o_pieces[c] = pc.pieces;
+      a.o_suf[c] = pc.suf;
+      a.o_sxm[c] = pc.sxm;
+      a.o_tail[c] = tail;
+      return true;
+    }
+    const u32x4* t4 = (const u32x4*)a.tile;
+    if constexpr (GROUPED) crc = crc_from_pieces4(start, mo, pc.suf, pc.sxm, tail, t4, e.t1, t);
+    else crc = crc_from_pieces(start, mo, pc.suf, pc.sxm, tail, t4, t);
   }
-  if (!(pieces & 4)) tail = tail_crc(a.file, mo);  // re-read the partial last line
-  const bool need_long = len >= 64;
-  // entries spanning many whole tiles combine them with one wave (slow_kernel)
-  const bool many_tiles = need_long && mo / TILE > start / TILE + 1 + LONG_TILES;
-  if (!need_long || ((pieces & 1) && (pieces & 2) && !many_tiles)) {
-    const uint32_t crc = crc_from_pieces(start, mo, suf, sxm, tail, a.tile);
-    a.o_crc[c] = crc;
-    a.o_ok[c] = crc == crc_st;
-    if (crc != crc_st) atomicAdd(a.n_bad, 1ull);
-    return false;
-  }
-  a.o_pieces[c] = pieces;
-  a.o_suf[c] = suf;
-  a.o_sxm[c] = sxm;
-  a.o_tail[c] = tail;
-  return true;
+  srd_gst(&a.o_crc[c], crc);
+  srd_gst(&a.o_ok[c], (uint8_t)(crc == e.crc_st));
+  if (crc != e.crc_st) atomicAdd(a.n_bad, 1ull);
+  return false;
 }
 
-
+// Chain entry c of the full pass (and the root entry of the optimistic one):
+// its candidate record gi (NO_REC: the root entry, from root_t -- no record,
+// no parent, start 0) and its parent's record pgi (< 0: the parent is the root
+// entry or lies outside the span).  Writes every output; true = slow_one needed.
+template <bool GROUPED, class T>
+__device__ bool finalize_core(const FinArgs& a, uint64_t c, uint64_t gi, int64_t pgi, uint64_t root_t,
+                              uint64_t* kh_out, const T& t) {
+  FinIn e;
+  uint64_t kh;
+  if (gi == NO_REC) {
+    e.mo = root_t - 20;
+    kh = ld_u64_unaligned(a.file, e.mo);
+    e.crc_st = ld_u32_unaligned(a.file, e.mo + 16);
+    e.p = 0;
+    e.fl = e.sxv = 0;
+  } else {
+    e.mo = a.c_m[gi];
+    const u32x4 r0 = a.c_rec[gi], r1 = a.c_rec1[gi];
+    e.p = (uint64_t)r0[0] | ((uint64_t)r0[1] << 32);
+    kh = (uint64_t)r1[0] | ((uint64_t)r1[1] << 32);
+    e.crc_st = r0[3];
+    e.fl = r0[2];
+    e.sxv = r1[2];
+  }
+  e.pfl = pgi >= 0 ? a.c_rec[pgi][2] : F_NO_PARENT;
+  e.psuf = pgi >= 0 ? a.c_rec1[pgi][3] : 0u;
+  const u32x4* t4 = (const u32x4*)a.tile;
+  e.t0 = t4[fin_start(e.fl, e.p) / TILE];
+  e.t1 = t4[e.mo / TILE];
+  *kh_out = kh;
+  a.o_mo[c] = e.mo;
+  a.o_kh[c] = kh;
+  if (a.o_packed) a.o_packed[c] = ((kh >> 48) << 48) | (e.mo & 0xFFFFFFFFFFFFull);  // key_indexer.rs:79-85
+  a.o_prev[c] = e.p;
+  a.o_crc_st[c] = e.crc_st;
+  return finalize_in<GROUPED>(a, c, e, t);
+}
 
 // Recompute, with one wave, SX at line j of tile k (bytes past flen read as 0;
 // the buffer is readable to srd_padded_size).  tab = the 4x256 CRC table in LDS.
@@ -2037,7 +1940,7 @@ __device__ __forceinline__ uint32_t mulp_wave(uint32_t a, uint32_t b, const uint
 struct SlowLds {
   uint32_t tab[1024];  // slice-by-4 CRC tables (tab[0..255]: the byte step R)
   uint32_t mx[1024];   // v -> v * X^64 byte tables
-  uint32_t m16k[1024];  // v -> v * x^16384 byte tables (tile_T's lower-half fix)
+  uint32_t m16k[1024];  // v -> v * x^16384 byte tables (lower_half)
   uint32_t invpow[4097];
   uint32_t xtile[65], xt64[65], winit[64], zero_crc[64];
   uint32_t x32768;
@@ -2068,8 +1971,7 @@ __device__ uint32_t crc_from_pieces_wave(uint64_t s, uint64_t m, uint32_t suf, u
   const uint64_t len = m - s;
   if (len < 64) return tail ^ L.zero_crc[len];
   const uint64_t k0 = s / TILE, k1 = m / TILE;
-  const uint32_t j0 = (uint32_t)((s % TILE) / 64);
-  uint32_t acc = suf ^ L.winit[j0];
+  uint32_t acc = suf ^ L.winit[line_of(s)];
   uint32_t y;
   if (k0 == k1) {
     y = acc ^ sxm;
@@ -2094,7 +1996,7 @@ __device__ uint32_t crc_from_pieces_wave(uint64_t s, uint64_t m, uint32_t suf, u
       for (int q = 0; q < 4; q++) {
         const uint64_t j = jb + 64 * q;
         if (j < n) {
-          h = mulfix(h, mx64) ^ mulfix(t0[q], L.m16k) ^ t2[q];  // h * X^64 ^ tile_T(k0 + 1 + j)
+          h = mulfix(h, mx64) ^ lower_half(t0[q], t2[q], L);  // h * X^64 ^ SX_0 of tile k0 + 1 + j
           jl = j;
           any = true;
         }
@@ -2105,7 +2007,7 @@ __device__ uint32_t crc_from_pieces_wave(uint64_t s, uint64_t m, uint32_t suf, u
     // acc * X^n ^ mid, then one more tile step into k1
     const uint32_t xn = n < 64 * 65 ? mulp_wave(L.xt64[n >> 6], L.xtile[n & 63], R) : xpow8_any(n * (uint64_t)TILE);
     acc = mulp_wave(xn, acc, R) ^ v;
-    y = mulp_wave(L.x32768, acc, R) ^ (mulfix(e0, L.m16k) ^ e2) ^ sxm;
+    y = mulp_wave(L.x32768, acc, R) ^ lower_half(e0, e2, L) ^ sxm;
   }
   const uint64_t dd = (k1 + 1) * TILE - m;
   return ~(mulp_wave(L.invpow[dd], y, R) ^ tail);
@@ -2124,8 +2026,8 @@ __device__ void slow_one(const FinArgs& a, uint64_t c, const SlowLds& L) {
   const uint64_t s = a.o_start[c], m = a.o_mo[c];
   const uint32_t pieces = a.o_pieces[c], tail = a.o_tail[c];
   uint32_t suf = a.o_suf[c], sxm = a.o_sxm[c];
-  if (!(pieces & 1)) suf = tile_probe_sx(a.file, a.flen, s / TILE, (uint32_t)((s % TILE) / 64), tab);
-  if (!(pieces & 2)) sxm = tile_probe_sx(a.file, a.flen, m / TILE, (uint32_t)((m % TILE) / 64), tab);
+  if (!(pieces & 1)) suf = tile_probe_sx(a.file, a.flen, s / TILE, line_of(s), tab);
+  if (!(pieces & 2)) sxm = tile_probe_sx(a.file, a.flen, m / TILE, line_of(m), tab);
   const uint32_t crc = crc_from_pieces_wave(s, m, suf, sxm, tail, a.tile, L);
   if ((threadIdx.x & 63) == 0) {
     a.o_crc[c] = crc;

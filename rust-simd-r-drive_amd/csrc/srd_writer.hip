@@ -37,25 +37,17 @@ __device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
   for (int o = 32; o > 0; o >>= 1) v ^= __shfl_xor(v, o);
   return v;
 }
-// v * x^16384 for a wave-uniform v by SCALAR loads of the byte tables (the
-// table words are uniform too: no LDS, no vector memory)
-__device__ __forceinline__ uint32_t mul16k_u(uint32_t v) {
-  const __attribute__((address_space(4))) uint32_t* m =
-      (const __attribute__((address_space(4))) uint32_t*)&g_tabs.m16k[0][0];
-  return m[v & 0xff] ^ m[256 + ((v >> 8) & 0xff)] ^ m[512 + ((v >> 16) & 0xff)] ^ m[768 + (v >> 24)];
-}
-// v * x^4096 (512 bytes) for a wave-uniform v by scalar loads
-__device__ __forceinline__ uint32_t mul4096_u(uint32_t v) {
-  const __attribute__((address_space(4))) uint32_t* m =
-      (const __attribute__((address_space(4))) uint32_t*)&g_tabs.m4096[0][0];
-  return m[v & 0xff] ^ m[256 + ((v >> 8) & 0xff)] ^ m[512 + ((v >> 16) & 0xff)] ^ m[768 + (v >> 24)];
-}
+// Table words at wave-uniform indexes by SCALAR loads (no LDS, no vector
+// memory): the table behind a constant-address-space pointer.  mulfix(v,
+// utab(g_tabs.m16k)) = v * x^16384 for a wave-uniform v, m4096: v * x^4096
+typedef const __attribute__((address_space(4))) uint32_t* utab_t;
+__device__ __forceinline__ utab_t utab(const uint32_t (&m)[4][256]) { return (utab_t)&m[0][0]; }
 // v * x^32768 (one 4 KiB block) = two x^16384 steps
-__device__ __forceinline__ uint32_t mul_tile_u(uint32_t v) { return mul16k_u(mul16k_u(v)); }
-// a table word at a wave-uniform index, by a scalar load
-__device__ __forceinline__ uint32_t tab_u(const uint32_t* p) {
-  return *(const __attribute__((address_space(4))) uint32_t*)p;
+__device__ __forceinline__ uint32_t mul_tile_u(uint32_t v) {
+  return mulfix(mulfix(v, utab(g_tabs.m16k)), utab(g_tabs.m16k));
 }
+// a table word at a wave-uniform index, by a scalar load
+__device__ __forceinline__ uint32_t tab_u(const uint32_t* p) { return *(utab_t)p; }
 // x^(8 n) mod P for a wave-uniform n (xpow8_dev with scalar table loads)
 __device__ __forceinline__ uint32_t xpow8_u(uint64_t n) {
   uint32_t r = kX0;
@@ -211,7 +203,7 @@ __global__ __launch_bounds__(SCAN_WAVES_V2 * 64, 1) void write_kernel(WriteArgs 
     const uint32_t nz = tomb ? 1u : (b == 0 && own_pad ? (uint32_t)pad : 0u);
     __builtin_amdgcn_raw_buffer_store_b8((uint8_t)0, out_rsrc(a.out + (e.tail - a.base), nz), (uint32_t)lane, 0, 0);
     bool done = tomb;
-    uint32_t crc = 0xD202EF8Du;  // CRC32(b"\0")
+    uint32_t crc = TOMB_CRC;
     uint64_t mo = e.tail + 1;
     if (!tomb) {
       uint8_t* dst = a.out + (st - a.base);  // 64-aligned when out is
@@ -284,7 +276,7 @@ __global__ __launch_bounds__(SCAN_WAVES_V2 * 64, 1) void write_kernel(WriteArgs 
       // raw CRC of this 4 KiB block (zero-padded past the payload)
       const uint32_t hx = V == 1 ? d[0] ^ d[15] : half_suffix_xor(lane_weight_or(crc_line4_wide(d, lds, R), nib_lane), lane);
       const uint32_t lo = __builtin_amdgcn_readlane(hx, 0), hi = __builtin_amdgcn_readlane(hx, 32);
-      const uint32_t raw = (CO ? mul4096_u(lo) : mul16k_u(lo)) ^ hi;
+      const uint32_t raw = mulfix(lo, utab(CO ? g_tabs.m4096 : g_tabs.m16k)) ^ hi;
       acc = b ? mul_tile_u(acc) ^ raw : raw;
       if (b + 1 == nb) {
         if (a.null_only && !__ballot(any != 0) && lane == 0) atomicOr(a.null_only, 1u);

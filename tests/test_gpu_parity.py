@@ -357,18 +357,44 @@ def test_mixed_sizes(ctx, flags):
     check_against_oracle(O.synth_store(len(lens), lens=lens), ctx, flags, "zipf")
 
 
-@pytest.mark.parametrize("flags", [0, S.SRD_FLAG_FORCE_FULL])
-def test_root_entry_metadata_lines(ctx, flags):
+# The finalize rule (csrc/srd_fin.h) runs on three routes: the fused optimistic
+# pass (flags 0: finalize_in in chain_finalize_kernel<true>, finalize_core for
+# the root entry), the full pass (SRD_FLAG_FORCE_FULL: finalize_core for every
+# entry) and the optimistic pass with the shape check as a kernel of its own
+# (UNFUSED: check_kernel + chain_finalize_kernel<false>, the retry rounds'
+# shape, on a context made under SRD_GLUE_FUSED=0).
+UNFUSED = "unfused"
+FIN_ROUTES = [0, S.SRD_FLAG_FORCE_FULL, UNFUSED]
+
+
+@pytest.fixture(scope="module")
+def unfused_ctx():
+    c = _ctx_with_env(SRD_GLUE_FUSED=0)
+    yield c
+    c.close()
+
+
+def check_on_route(data, ctx, unfused_ctx, route, name):
+    """check_against_oracle on one of FIN_ROUTES."""
+    if route != UNFUSED:
+        return check_against_oracle(data, ctx, route, name)
+    r = check_against_oracle(data, unfused_ctx, 0, f"unfused:{name}")
+    assert r.mode == S.SRD_MODE_OPTIMISTIC, (name, r.mode, r.full_reason)
+    return r
+
+
+@pytest.mark.parametrize("flags", FIN_ROUTES)
+def test_root_entry_metadata_lines(ctx, unfused_ctx, flags):
     # the root entry (prev 0) has no candidate record: finalize takes its
     # metadata-line suffix from the per-tile values for lines 0 / 1 / 32 of a
     # tile, the slow kernel otherwise -- every first-entry length class
     for first in [4096, 8192, 64, 100, 127, 2048, 2100, 4160, 4200, 6144 + 40, 12288, 3000, 20, 63, 1 << 17]:
         lens = np.array([first] + [4096, 77, 2048, 5000] * 3, np.uint64)
-        check_against_oracle(O.synth_store(len(lens), lens=lens), ctx, flags, f"root{first}")
+        check_on_route(O.synth_store(len(lens), lens=lens), ctx, unfused_ctx, flags, f"root{first}")
 
 
-@pytest.mark.parametrize("flags", [0, S.SRD_FLAG_FORCE_FULL])
-def test_whole_tile_counts_around_the_inline_limit(ctx, flags):
+@pytest.mark.parametrize("flags", FIN_ROUTES)
+def test_whole_tile_counts_around_the_inline_limit(ctx, unfused_ctx, flags):
     # a finalize lane combines up to LONG_TILES (16) whole tiles itself, a
     # longer entry takes the slow list (a wave each): entries of 1..22 whole
     # tiles between their start and metadata tiles, at shifting alignments
@@ -379,10 +405,10 @@ def test_whole_tile_counts_around_the_inline_limit(ctx, flags):
         for d in (-70, -1, 0, 1, 63, 2100):
             lens += [w * 4096 + d, rnd.choice([20, 77, 1000, 4095, 2048 + 7])]
     lens = np.array(lens, np.uint64)
-    check_against_oracle(O.synth_store(len(lens), lens=lens), ctx, flags, "tiles")
+    check_on_route(O.synth_store(len(lens), lens=lens), ctx, unfused_ctx, flags, "tiles")
 
 
-def test_tombstones_and_overwrites_random(ctx):
+def test_tombstones_and_overwrites_random(ctx, unfused_ctx):
     rnd = random.Random(11)
     buf = bytearray()
     t = 0
@@ -397,8 +423,8 @@ def test_tombstones_and_overwrites_random(ctx):
             if pl == b"\x00":
                 pl = b"\x01"
             t = O.write_entries(buf, t, [(kh, pl)])
-    for flags in (0, S.SRD_FLAG_FORCE_FULL):
-        check_against_oracle(bytes(buf), ctx, flags, "tomb")
+    for flags in FIN_ROUTES:
+        check_on_route(bytes(buf), ctx, unfused_ctx, flags, "tomb")
 
 
 def test_torn_and_corrupted(ctx):

@@ -47,6 +47,20 @@ def test_scan_partition_arithmetic_sanitized():
     assert p.returncode == 0 and "part_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
 
 
+def test_finalize_rule_sanitized():
+    """csrc/srd_fin.h (the finalize rule: an entry's CRC from the scan's pieces, the code finalize_core,
+    finalize_in and the slow path run) as a stand-alone host program under ASan + UBSan: over every start-line and
+    metadata-line class and 0..22 whole tiles between them the serial and the grouped crc_from_pieces equal a
+    byte-wise CRC-32; short entries; every fin_pieces branch resolves the byte-wise suffix or leaves the piece
+    missing; fin_route sends exactly the entries with a missing piece or more than LONG_TILES whole tiles to the
+    slow list (tests/sanitize/fin_check.cpp)."""
+    d = os.path.join(ROOT, "tests", "sanitize")
+    subprocess.check_call(["make", "-s", "-C", d, "build/fin_check"])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    p = subprocess.run([os.path.join(d, "build", "fin_check")], capture_output=True, text=True, env=env, timeout=600)
+    assert p.returncode == 0 and "fin_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
+
+
 def _abi_check_bin():
     d = os.path.join(ROOT, "tests", "abi_c")
     if not os.path.exists(S.LIB_PATH):
