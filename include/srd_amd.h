@@ -599,6 +599,54 @@ int srd_compact_device(srd_ctx *ctx, const uint8_t *d_file, uint64_t file_len,
                        uint8_t *d_out, uint64_t out_cap, uint64_t *new_len,
                        uint64_t *d_key_hash_out, uint64_t *d_meta_off_out);
 
+/* ---- verified payloads: batched gather with checksum check ----
+ *   srd_payload_gather_device <- what a reader does with the handles a read
+ *                                returns: EntryHandle::as_slice plus
+ *                                EntryHandle::is_valid_checksum
+ *                                (simd-r-drive-entry-handle/src/entry_handle.rs:260-275),
+ *                                for a whole batch of ranges
+ * d_start / d_end are n payload ranges [start, end) as the read and iterator
+ * calls above write them (srd_device_result's payload_start / meta_off work as
+ * they are): end is the entry's metadata offset, the stored checksum the
+ * little-endian u32 at d_file[end + 16 .. end + 20).  The ranges are the
+ * caller's: a range that does not lie inside the file with its metadata is
+ * refused by arithmetic (SRD_GATHER_BAD_RANGE) and nothing of it is read; no
+ * byte outside [0, file_len) is read because of any range.  Any start alignment
+ * gives the right bytes and CRC; 64-aligned starts (every real entry) are the
+ * fast path.
+ * Output: d_out_off[i] = the exclusive sum of roundup64(end - start) over the
+ * queries with status OK or BAD_CRC, d_out_off[n] = the total (also *total);
+ * payload i lies at d_out[d_out_off[i] ..) and the bytes up to the next
+ * 64-byte boundary are written as zero; no byte at or past the total is
+ * touched.  d_out must be 16-byte aligned.  d_crc_computed[i] (nullable) =
+ * crc32(payload i), 0 for NONE / BAD_RANGE.
+ *   d_out == NULL without SRD_GATHER_VERIFY_ONLY: the layout only -- d_out_off,
+ *     *total and the NONE / BAD_RANGE statuses (the statuses of the other
+ *     queries and d_crc_computed are left as they are);
+ *   SRD_GATHER_VERIFY_ONLY: d_out is ignored and never written; statuses and
+ *     CRCs are complete (a batched is_valid_checksum).
+ * SRD_ERR_ARG, nothing written but *total: the total exceeds out_cap; [d_out,
+ * d_out + out_cap) overlaps the store's padded range; n >= 2^31; the
+ * batch has 2^32 or more work units.
+ * Ordered on `stream`; waits once, for the total, and returns with the copy
+ * enqueued: later work on `stream` sees the outputs.  The workspace comes
+ * from the context (srd_ctx_device_bytes counts it). */
+#ifndef SRD_GATHER_CHUNK
+#define SRD_GATHER_CHUNK 65536u   /* work-unit size in bytes, a multiple of 4096 (measured: DESIGN.md section 11) */
+#endif
+#define SRD_GATHER_VERIFY_ONLY 1u /* compute statuses and CRCs, copy nothing */
+/* d_status values */
+#define SRD_GATHER_NONE 0u       /* start == end (a read's None): nothing copied */
+#define SRD_GATHER_OK 1u         /* copied, crc32(payload) == the stored checksum */
+#define SRD_GATHER_BAD_CRC 2u    /* copied faithfully, checksum differs */
+#define SRD_GATHER_BAD_RANGE 3u  /* start > end, or end + 20 > file_len: nothing read, nothing copied */
+int srd_payload_gather_device(srd_ctx *ctx, const uint8_t *d_file, uint64_t file_len,
+                              const uint64_t *d_start, const uint64_t *d_end, uint64_t n,
+                              uint32_t flags, uint8_t *d_out, uint64_t out_cap,
+                              uint64_t *d_out_off /* n + 1 */, uint8_t *d_status /* n */,
+                              uint32_t *d_crc_computed /* n, nullable */,
+                              uint64_t *total, void *stream);
+
 /* Synthetic store of the BASELINE configs written on the device (the
  * checksum-on-append writer of data_store.rs:847-939 for keys
  * "bench-key-{i}" and counter-mode splitmix64 payloads).  lens==NULL ->

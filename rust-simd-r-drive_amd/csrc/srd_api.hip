@@ -11,6 +11,8 @@
 //     srd_kernels.hip         scan, link, full-pass glue, finalize (one entry: finalize_in), slow path, batch digests, synth
 //     srd_glue.hip            sync-free glue of the optimistic pass (shape test, entry pass), bucketed index, owner partition
 //     srd_writer.hip          batch writer
+//     srd_gather.h            the payload gather's range rule, unit / chunk arithmetic and CRC combine (a CPU check uses it too)
+//     srd_gather.hip          verified payloads: batched gather with checksum check (uses the writer's helpers)
 //     srd_index.hip           lookup table, batched reads, iterator, compaction
 //     srd_index_live.hip      the table kept live: apply, export, batched delete
 //     srd_probe.hip           stream probe
@@ -23,7 +25,7 @@
 //     srd_host_input.hip      staging, pinned host results, host-pointer entries
 //     srd_multi.hip           multi-GPU open
 //     srd_ops.hip             probe, batch digests, synth, writer, table / reads / maintenance, iterator,
-//                             compaction
+//                             compaction, payload gather
 //   this file               error / build-info entries, stamps read-outs, host self-test
 //
 // Glue scans/compactions use hipCUB (library primitives, like calling
@@ -51,6 +53,8 @@
 #include "srd_kernels.hip"
 #include "srd_glue.hip"
 #include "srd_writer.hip"
+#include "srd_gather.h"
+#include "srd_gather.hip"
 #include "srd_index.hip"
 #include "srd_index_live.hip"
 #include "srd_probe.hip"

@@ -681,3 +681,106 @@ extern "C" int srd_compact_device(srd_ctx* c, const uint8_t* d_file, uint64_t fl
   }
   return 0;
 }
+
+// ---------------------------------------------------------------------------
+// Verified payloads (srd_gather.hip): layout, one wait for the total, then the
+// unit table, the gather, the combine and the finish enqueued on the stream
+static int gather_scan(Ctx* c, const uint64_t* in, uint64_t* out, uint64_t n, hipStream_t s) {
+  size_t tb = c->bufs[B_CUB_TMP].n;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(P<void>(c, B_CUB_TMP), tb, in, out, (int)n, s));
+  return 0;
+}
+
+extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint64_t flen, const uint64_t* d_start,
+                                         const uint64_t* d_end, uint64_t n, uint32_t flags, uint8_t* d_out,
+                                         uint64_t out_cap, uint64_t* d_out_off, uint8_t* d_status,
+                                         uint32_t* d_crc_computed, uint64_t* total, void* stream) {
+  const bool verify = flags & SRD_GATHER_VERIFY_ONLY;
+  if (verify) d_out = nullptr;
+  if (!c || !total || !d_out_off || n >= (1ull << 31) || (flags & ~SRD_GATHER_VERIFY_ONLY) ||
+      (n && (!d_start || !d_end || !d_status || (flen && !d_file))) || ((uintptr_t)d_out & 15)) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  *total = 0;
+  if (d_out) {  // the output may not lie in what the store's kernels read (srd_padded_size)
+    const uintptr_t f0 = (uintptr_t)d_file, f1 = f0 + srd_padded_size(flen), o0 = (uintptr_t)d_out, o1 = o0 + out_cap;
+    if (d_file && out_cap && o0 < f1 && f0 < o1) {
+      set_err("d_out overlaps the store");
+      return SRD_ERR_ARG;
+    }
+  }
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if (!n) {
+    HIPCHK(hipMemsetAsync(d_out_off, 0, 8, s));
+    return 0;
+  }
+  TRY(ensure(c, B_GA_ST, n));
+  TRY(ensure(c, B_GA_PLEN, n * 8));
+  TRY(ensure(c, B_GA_CHK, n * 8));
+  TRY(ensure(c, B_GA_OFF, n * 8));
+  TRY(ensure(c, B_GA_CPRE, n * 8));
+  TRY(ensure(c, B_GA_CRC, n * 4));
+  TRY(ensure(c, B_GA_CNT, 64));
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n));
+  TRY(ensure(c, B_CUB_TMP, tb + 256));
+  PayloadGatherArgs a{};
+  a.file = d_file;
+  a.flen = flen;
+  a.start = d_start;
+  a.end = d_end;
+  a.n = n;
+  a.st = P<uint8_t>(c, B_GA_ST);
+  a.plen = P<uint64_t>(c, B_GA_PLEN);
+  a.chk = P<uint64_t>(c, B_GA_CHK);
+  a.off = P<uint64_t>(c, B_GA_OFF);
+  a.cpre = P<uint64_t>(c, B_GA_CPRE);
+  a.cnt = P<unsigned long long>(c, B_GA_CNT);
+  a.crc = P<uint32_t>(c, B_GA_CRC);
+  a.out = d_out;
+  a.o_off = d_out_off;
+  a.o_status = d_status;
+  a.o_crc = d_crc_computed;
+  a.layout_only = !d_out && !verify;
+  HIPCHK(hipMemsetAsync(a.cnt, 0, 8, s));
+  payload_layout_kernel<<<grid_for(n), 256, 0, s>>>(a);
+  HIPCHK(hipGetLastError());
+  TRY(gather_scan(c, a.plen, a.off, n, s));
+  TRY(gather_scan(c, a.chk, a.cpre, n, s));
+  // the totals = the last query's exclusive sum + its own term (n items: n < 2^31 fits hipCUB's int count)
+  uint64_t* h = c->h_small + 24;
+  HIPCHK(hipMemcpyAsync(h, a.off + n - 1, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h + 1, a.plen + n - 1, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h + 2, a.cpre + n - 1, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h + 3, a.chk + n - 1, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h + 4, a.cnt, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(spin_sync(s));
+  const uint64_t tot = h[0] + h[1], units = h[2] + h[3], n_multi = h[4];
+  *total = tot;
+  a.total = tot;
+  if (d_out && tot > out_cap) {
+    set_err("out_cap too small for the gathered payloads: " + std::to_string(tot) + " bytes");
+    return SRD_ERR_ARG;
+  }
+  if (units >= (1ull << 32)) { set_err("too many work units in one batch"); return SRD_ERR_ARG; }
+  if (!a.layout_only && units) {
+    TRY(ensure(c, B_GA_UNIT, units * 4));
+    TRY(ensure(c, B_GA_RAW, units * 4));
+    a.unit_hit = P<uint32_t>(c, B_GA_UNIT);
+    a.raw = P<uint32_t>(c, B_GA_RAW);
+    a.n_units = units;
+    payload_units_kernel<<<grid_for(units), 256, 0, s>>>(a);
+    const unsigned g = (unsigned)std::min<uint64_t>((units + SCAN_WAVES_V2 - 1) / SCAN_WAVES_V2, c->scan_blocks);
+    payload_gather_kernel<<<g, SCAN_WAVES_V2 * 64, 0, s>>>(a);
+    if (n_multi) payload_combine_kernel<<<(unsigned)std::min<uint64_t>((n + 3) / 4, 4096), 256, 0, s>>>(a);
+  }
+  payload_finish_kernel<<<grid_for(n + 1), 256, 0, s>>>(a);
+  HIPCHK(hipGetLastError());
+  if (sync_debug()) {
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
+}

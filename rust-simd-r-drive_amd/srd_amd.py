@@ -71,6 +71,7 @@ EXPORTS = [
     "srd_validate_index_multi_device", "srd_ctx_multi_summary", "srd_ctx_scan_list", "srd_ctx_set_timing_every",
     "srd_stream_probe_device", "srd_ctx_multi_shard_ms",
     "srd_index_table_apply_device", "srd_index_table_export_device", "srd_batch_delete_hashed_device",
+    "srd_payload_gather_device",
 ]
 
 
@@ -198,6 +199,8 @@ def lib():
         L.srd_index_table_export_device.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
         L.srd_batch_delete_hashed_device.argtypes = [vp, vp, u64, C.POINTER(u64), vp, u64, u64, vp, u64,
                                                      C.POINTER(u64), C.POINTER(u64)]
+        L.srd_payload_gather_device.argtypes = [vp, vp, u64, vp, vp, u64, u32, vp, u64, vp, vp, vp,
+                                                C.POINTER(u64), vp]
         L.srd_iter_entries_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
         L.srd_estimate_compaction_savings_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.srd_compact_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, vp]
@@ -850,6 +853,90 @@ def _ctx_device(ctx: Context) -> int:
 
 INDEX_NONE = (1 << 64) - 1
 
+# srd_payload_gather_device (include/srd_amd.h)
+GATHER_CHUNK = 65536  # SRD_GATHER_CHUNK: the work-unit size in bytes
+GATHER_VERIFY_ONLY = 1
+GATHER_NONE, GATHER_OK, GATHER_BAD_CRC, GATHER_BAD_RANGE = 0, 1, 2, 3
+
+
+class GatherResult:
+    """What srd_payload_gather_device wrote for n queries: `data` (uint8 device
+    tensor of the total: payload i at data[offs[i] : offs[i] + lens[i]], zero up
+    to the next 64-byte boundary; None after a verify-only call), and the host
+    arrays `offs` (n + 1), `lens`, `status` (GATHER_*) and `crc_computed`."""
+
+    def __init__(self, data, offs, lens, status, crc_computed):
+        self.data, self.offs, self.lens, self.status, self.crc_computed = data, offs, lens, status, crc_computed
+
+    def __len__(self):
+        return len(self.status)
+
+    def payloads(self):
+        """[payload bytes | None] in query order (None: no hit), by one copy to the host."""
+        if self.data is None:
+            raise ValueError("a verify-only gather holds no payload bytes")
+        flat = self.data.cpu().numpy().tobytes() if self.data.numel() else b""
+        return [flat[int(o): int(o) + int(n)] if s in (GATHER_OK, GATHER_BAD_CRC) else None
+                for o, n, s in zip(self.offs, self.lens, self.status)]
+
+    def is_valid_checksum(self):
+        """EntryHandle::is_valid_checksum per query: [bool | None] (None: no hit)."""
+        return [True if s == GATHER_OK else False if s == GATHER_BAD_CRC else None for s in self.status]
+
+
+def payload_gather_device(d_file: int, file_len: int, d_start: int, d_end: int, n: int, flags: int = 0,
+                          d_out: int | None = None, out_cap: int = 0, d_out_off: int | None = None,
+                          d_status: int | None = None, d_crc_computed: int | None = None,
+                          ctx: "Context | None" = None, stream: int | None = None) -> int:
+    """srd_payload_gather_device as it is (device pointers in, the total out):
+    ordered on `stream` (default: the context stream), returns with the copy
+    enqueued.  SrdError carries SRD_ERR_ARG's message; `.total` is set on it when
+    the capacity was the reason."""
+    ctx = ctx or default_ctx()
+    tot = C.c_uint64()
+    rc = lib().srd_payload_gather_device(ctx.h, C.c_void_p(d_file), file_len, C.c_void_p(d_start), C.c_void_p(d_end), n,
+                                         flags, C.c_void_p(d_out), out_cap, C.c_void_p(d_out_off),
+                                         C.c_void_p(d_status), C.c_void_p(d_crc_computed), C.byref(tot),
+                                         C.c_void_p(stream if stream is not None else ctx.stream))
+    if rc != 0:
+        e = SrdError(f"srd error {rc}: {lib().srd_last_error().decode()}")
+        e.rc, e.total = rc, int(tot.value)
+        raise e
+    return int(tot.value)
+
+
+def gather_ranges(d_file: int, file_len: int, st, en, flags: int = 0, ctx: "Context | None" = None) -> GatherResult:
+    """The payloads of the ranges [st[i], en[i]) (device int64 tensors, as the
+    read and iterator calls write them) gathered into one device buffer and
+    checked against their stored checksums: the layout call sizes the buffer,
+    the full call fills it.  §10's stream rule: the context stream waits for
+    torch's current stream first, the host for the context stream at the end."""
+    import torch
+    ctx = ctx or default_ctx()
+    dev, n = st.device, st.numel()
+    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    crc = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    lib_stream = torch.cuda.ExternalStream(ctx.stream, device=dev)
+    lib_stream.wait_stream(torch.cuda.current_stream(dev))
+    args = (d_file, file_len, st.data_ptr(), en.data_ptr(), n)
+    data = None
+    if flags & GATHER_VERIFY_ONLY:
+        payload_gather_device(*args, flags, None, 0, offs.data_ptr(), status.data_ptr(), crc.data_ptr(), ctx)
+    else:
+        total = payload_gather_device(*args, flags, None, 0, offs.data_ptr(), status.data_ptr(), None, ctx)
+        data = torch.empty(total, dtype=torch.uint8, device=dev)
+        lib_stream.wait_stream(torch.cuda.current_stream(dev))
+        # (no hit at all: nothing to copy, the verify-only call completes statuses and CRCs)
+        payload_gather_device(*args, flags if total else flags | GATHER_VERIFY_ONLY, data.data_ptr() if total else None,
+                              total, offs.data_ptr(), status.data_ptr(), crc.data_ptr(), ctx)
+    lib_stream.synchronize()
+    o = offs.cpu().numpy().view(np.uint64)
+    s = status[:n].cpu().numpy()
+    ln = (en - st).cpu().numpy().view(np.uint64).copy()
+    ln[(s != GATHER_OK) & (s != GATHER_BAD_CRC)] = 0
+    return GatherResult(data, o, ln, s, crc[:n].cpu().numpy().view(np.uint32))
+
 
 class DeviceIndex:
     """The KeyIndexer adopted on the GPU: an open-addressing table in HBM built
@@ -1007,6 +1094,33 @@ class DeviceIndex:
         torch.cuda.synchronize()
         s, e = st.cpu().numpy().view(np.uint64), en.cpu().numpy().view(np.uint64)
         return [None if a == b else (int(a), int(b)) for a, b in zip(s, e)]
+
+    def _ranges_device(self, d_file: int, file_len: int, hashes, verify=None):
+        """srd_batch_read_hashed_device on the context stream: the ranges stay on
+        the device (two int64 tensors), nothing waits."""
+        import torch
+        q = self._as_dev(hashes)
+        v = self._as_dev(verify) if verify is not None else None
+        st, en = torch.empty_like(q), torch.empty_like(q)
+        self._lib_after_torch()
+        _check(lib().srd_batch_read_hashed_device(self.ctx.h, C.c_void_p(self.table.data_ptr()), self.nbytes,
+                                                  C.c_void_p(d_file), file_len, C.c_void_p(q.data_ptr()),
+                                                  C.c_void_p(v.data_ptr()) if v is not None else None, q.numel(),
+                                                  C.c_void_p(st.data_ptr()), C.c_void_p(en.data_ptr()),
+                                                  C.c_void_p(self.ctx.stream)))
+        return st, en, (q, v)  # (the inputs live until the caller has waited)
+
+    def batch_gather(self, d_file: int, file_len: int, hashes, non_hashed_keys=None, flags: int = 0) -> GatherResult:
+        """batch_read_hashed_keys with the payloads: the look-up and the verified
+        gather (srd_payload_gather_device) on the device, one GatherResult in query
+        order -- a read's bytes plus EntryHandle::is_valid_checksum for each."""
+        if non_hashed_keys is not None and len(non_hashed_keys) != len(hashes):
+            raise ValueError("Mismatched lengths for hashed and non-hashed keys.")
+        v = compute_hash_batch(non_hashed_keys, self.ctx) if non_hashed_keys is not None else None
+        st, en, keep = self._ranges_device(d_file, file_len, hashes, v)
+        r = gather_ranges(d_file, file_len, st, en, flags, self.ctx)
+        del keep
+        return r
 
     def batch_read(self, d_file: int, file_len: int, keys):
         """batch_read (data_store.rs:1111-1115): host keys, hashed and verified on the device."""
@@ -1252,3 +1366,43 @@ class DeviceStore:
     def exists(self, key: bytes) -> bool:
         """DataStoreReader::exists (data_store.rs:1030-1032): read(key).is_some()."""
         return self.read(key) is not None
+
+    # -- verified reads: the payloads gathered and checked on the device --------------------
+
+    def batch_gather(self, keys, flags: int = 0) -> GatherResult:
+        """batch_read with EntryHandle::is_valid_checksum on every handle: the
+        payloads of `keys` gathered into one device buffer, each checked against
+        its stored checksum (every read verified by its key's own tag)."""
+        h = compute_hash_batch(keys, self.ctx) if len(keys) else []
+        return self._gather_hashed(h, h, flags)
+
+    def _gather_hashed(self, hashes, verify, flags):
+        st, en, keep = self.index._ranges_device(self.buf.data_ptr(), self._tail, hashes, verify)
+        r = gather_ranges(self.buf.data_ptr(), self._tail, st, en, flags, self.ctx)
+        del keep
+        return r
+
+    def batch_gather_hashed_keys(self, hashes, non_hashed_keys=None, flags: int = 0) -> GatherResult:
+        """batch_read_hashed_keys (data_store.rs:1111-1158) with the payloads verified."""
+        return self.index.batch_gather(self.buf.data_ptr(), self._tail, hashes, non_hashed_keys, flags)
+
+    def verify(self, keys):
+        """The batched is_valid_checksum of `keys` (no payload is copied):
+        [True | False | None (no such key)] in query order."""
+        return self.batch_gather(keys, GATHER_VERIFY_ONLY).is_valid_checksum()
+
+    def iter_gather(self) -> GatherResult:
+        """Every live payload in EntryIterator order (newest first), gathered and
+        verified: the index's export, srd_iter_entries_device, then the gather of
+        its ranges."""
+        import torch
+        _k, p = self.index.export()  # synchronises
+        n = p.numel()
+        outs = [torch.empty(max(n, 1), dtype=torch.int64, device=self.buf.device) for _ in range(4)]
+        got = C.c_uint64()
+        self.index._lib_after_torch()
+        _check(lib().srd_iter_entries_device(self.ctx.h, C.c_void_p(self.buf.data_ptr()), self._tail,
+                                             C.c_void_p(p.data_ptr()), n, *[C.c_void_p(t.data_ptr()) for t in outs],
+                                             C.byref(got)))  # synchronises
+        k = int(got.value)
+        return gather_ranges(self.buf.data_ptr(), self._tail, outs[0][:k], outs[1][:k], 0, self.ctx)
