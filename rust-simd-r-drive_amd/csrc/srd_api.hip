@@ -13,12 +13,16 @@
 //     srd_writer.hip          batch writer
 //     srd_gather.h            the payload gather's range rule, unit / chunk arithmetic and CRC combine (a CPU check uses it too)
 //     srd_gather.hip          verified payloads: batched gather with checksum check (uses the writer's helpers)
-//     srd_index.hip           lookup table, batched reads, iterator, compaction
+//     srd_table.h             the lookup table's rule: slot states, probe, claim, size arithmetic (the host entries
+//                             and a CPU check use it too)
+//     srd_index.hip           lookup table build and reads, iterator, compaction
 //     srd_index_live.hip      the table kept live: apply, export, batched delete
 //     srd_probe.hip           stream probe
 //   host code (in include order: each file uses only the ones above it)
 //     srd_host.cpp / .h       no-HIP parsers (shard cuts, batch layout)
-//     srd_ctx.hip             errors, context + workspace, table upload, knobs, create / destroy, timing
+//     srd_ctx.hip             errors, the launch check (LAUNCHED), context + workspace, table upload, the pinned
+//                             read-back of small results (read_small), the hipCUB wrappers and their scratch,
+//                             knobs, create / destroy, timing
 //     srd_scan_host.hip       scan geometry, workspace and launch, load-pattern trial
 //     srd_index_build.hip     bucketed / global index build, owner partition, their entries
 //     srd_validate.hip        optimistic pass, full pass, finish; the two validate entries
@@ -55,6 +59,7 @@
 #include "srd_writer.hip"
 #include "srd_gather.h"
 #include "srd_gather.hip"
+#include "srd_table.h"
 #include "srd_index.hip"
 #include "srd_index_live.hip"
 #include "srd_probe.hip"

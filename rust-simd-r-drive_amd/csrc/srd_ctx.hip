@@ -1,9 +1,11 @@
 // srd_ctx.hip -- the context and its workspace (included by srd_api.hip).
 //
-// Error reporting (g_err, HIPCHK / KCHK / TRY), the context struct and its
-// buffer table, the CRC table upload, the small stream helpers every host
-// file uses, the environment knobs, srd_ctx_create / destroy / getters and
-// the timing entries.
+// Error reporting (g_err, HIPCHK / TRY, the launch check LAUNCHED), the
+// context struct and its buffer table, the CRC table upload, the small helpers
+// every host file uses (spin_sync, stream_of, the pinned read-back read_small
+// and the validate counters, the hipCUB wrappers: the only users of h_small
+// and B_CUB_TMP), the environment knobs, srd_ctx_create / destroy / getters
+// and the timing entries.
 static thread_local std::string g_err;
 static void set_err(const std::string& s) { g_err = s; }
 
@@ -18,25 +20,28 @@ static void set_err(const std::string& s) { g_err = s; }
 
 namespace {
 
-// SRD_SYNC_DEBUG=1: synchronise after every kernel and name the first one
-// that fails (debugging aid; off by default)
-static int sync_debug() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("SRD_SYNC_DEBUG"); v = (e && *e && *e != '0') ? 1 : 0; }
-  return v;
-}
-#define KCHK(c, name)                                                                           \
-  do {                                                                                          \
-    if (sync_debug()) {                                                                         \
-      hipError_t e_ = hipStreamSynchronize((c)->stream);                                        \
-      if (e_ == hipSuccess) e_ = hipGetLastError();                                             \
-      if (e_ != hipSuccess) {                                                                   \
-        set_err(std::string("kernel ") + name + ": " + hipGetErrorString(e_));                  \
-        fprintf(stderr, "srd: kernel %s failed: %s\n", name, hipGetErrorString(e_));            \
-        return SRD_ERR_HIP;                                                                     \
-      }                                                                                         \
-    }                                                                                           \
+#define TRY(x)                 \
+  do {                         \
+    int r_ = (x);              \
+    if (r_) return r_;         \
   } while (0)
+
+// The check behind every kernel launch and hipCUB call on stream s: the launch
+// error, always; with SRD_SYNC_DEBUG=1 (a debugging aid, read once per
+// process) also a wait for s -- the stream the kernel went to -- and the name
+// of the kernel that failed.
+static int launched(hipStream_t s, const char* name) {
+  static const bool sync = [] { const char* e = getenv("SRD_SYNC_DEBUG"); return e && *e && *e != '0'; }();
+  HIPCHK(hipGetLastError());
+  if (!sync) return 0;
+  hipError_t e = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) return 0;
+  set_err(std::string("kernel ") + name + ": " + hipGetErrorString(e));
+  fprintf(stderr, "srd: kernel %s failed: %s\n", name, hipGetErrorString(e));
+  return SRD_ERR_HIP;
+}
+#define LAUNCHED(s, name) TRY(launched(s, name))
 
 struct Buf {
   void* p = nullptr;
@@ -322,12 +327,6 @@ int upload_tables() {
 
 inline unsigned blocks(uint64_t n, unsigned t) { return (unsigned)((n + t - 1) / t); }
 
-#define TRY(x)                 \
-  do {                         \
-    int r_ = (x);              \
-    if (r_) return r_;         \
-  } while (0)
-
 // hipCUB temp size for all glue ops up to n elements
 int ensure_cub(Ctx* c, uint64_t n) {
   size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0;
@@ -340,23 +339,6 @@ int ensure_cub(Ctx* c, uint64_t n) {
   t5 = std::max(std::max(t1, t2), std::max(t3, t4));
   return ensure(c, B_CUB_TMP, t5 + 256);
 }
-// the glue's two hipCUB scans over n elements on the context's stream, with
-// the scratch ensure_cub sized: inclusive max-scan and exclusive sum
-template <class In, class Out>
-static int scan_max(Ctx* c, In in, Out out, uint64_t n) {
-  size_t tb = c->bufs[B_CUB_TMP].n;
-  HIPCHK(hipcub::DeviceScan::InclusiveScan(P<void>(c, B_CUB_TMP), tb, in, out, hipcub::Max(), (int)n, c->stream));
-  KCHK(c, "hipcub");
-  return 0;
-}
-template <class In, class Out>
-static int scan_sum(Ctx* c, In in, Out out, uint64_t n) {
-  size_t tb = c->bufs[B_CUB_TMP].n;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(P<void>(c, B_CUB_TMP), tb, in, out, (int)n, c->stream));
-  KCHK(c, "hipcub");
-  return 0;
-}
-
 static bool debug_env() {
   static const bool v = [] { const char* e = getenv("SRD_DEBUG"); return e && *e && *e != '0'; }();
   return v;
@@ -370,23 +352,97 @@ static hipError_t spin_sync(hipStream_t s) {
   }
   return e;
 }
+// the stream of an entry that takes one (nullptr = the context's)
+static hipStream_t stream_of(Ctx* c, void* stream) { return stream ? (hipStream_t)stream : c->stream; }
 
-// the 8 counters into pinned h_small[0..8) (no wait) / with the wait: the
-// counters and, if extra != nullptr, the n_extra words enqueued into
-// h_small[8..) before (one host wait for all of them; a copy into pageable
-// memory would wait by itself)
+// Small device reads go through the pinned h_small (a copy into pageable
+// memory would wait by itself): words [0, 8) are the validate counters',
+// words [8, 32) serve one read_small at a time, which enqueues its reads on
+// s, waits once and hands the values to their destinations -- nothing is left
+// in the pinned area, so a caller may hold values across another such read.
+struct SmallRead {
+  const void* src;  // device
+  void* dst;        // host
+  size_t bytes;     // 0: skipped
+};
+template <class T>
+static SmallRead rd(const T* src, T* dst) { return SmallRead{src, dst, sizeof(T)}; }
+static int read_small(Ctx* c, hipStream_t s, std::initializer_list<SmallRead> reads) {
+  uint64_t* w = c->h_small + 8;  // each read takes whole words
+  for (const SmallRead& r : reads) {
+    if (w + (r.bytes + 7) / 8 > c->h_small + 32) { set_err("internal: read_small over its pinned area"); return SRD_ERR_INTERNAL; }
+    if (r.bytes) HIPCHK(hipMemcpyAsync(w, r.src, r.bytes, hipMemcpyDeviceToHost, s));
+    w += (r.bytes + 7) / 8;
+  }
+  HIPCHK(spin_sync(s));
+  w = c->h_small + 8;
+  for (const SmallRead& r : reads) {
+    if (r.bytes) memcpy(r.dst, w, r.bytes);
+    w += (r.bytes + 7) / 8;
+  }
+  return 0;
+}
+// The 8 validate counters into h_small[0, 8).  Two phases where the copy rides
+// on somebody else's wait (finish: the index build's); read_counters = both
+// with a wait of its own, which one more u64 (extra_src, nullable) shares.
 static int enqueue_counters(Ctx* c) {
   HIPCHK(hipMemcpyAsync(c->h_small, P<uint64_t>(c, B_COUNTERS), 8 * 8, hipMemcpyDeviceToHost, c->stream));
   return 0;
 }
-static int enqueue_small(Ctx* c, const void* src, uint32_t word) {  // one u64 into h_small[8 + word]
-  HIPCHK(hipMemcpyAsync(c->h_small + 8 + word, src, 8, hipMemcpyDeviceToHost, c->stream));
+static void counters_landed(Ctx* c, uint64_t* h) { memcpy(h, c->h_small, 64); }
+int read_counters(Ctx* c, uint64_t* h, const uint64_t* extra_src = nullptr, uint64_t* extra = nullptr) {
+  TRY(enqueue_counters(c));
+  if (extra_src) TRY(read_small(c, c->stream, {rd(extra_src, extra)}));
+  else HIPCHK(spin_sync(c->stream));
+  counters_landed(c, h);
   return 0;
 }
-int read_counters(Ctx* c, uint64_t* h) {
-  TRY(enqueue_counters(c));
-  HIPCHK(spin_sync(c->stream));
-  memcpy(h, c->h_small, 64);
+
+// hipCUB on stream s (nullptr = the context's) with the scratch in B_CUB_TMP,
+// which the caller sized before: ensure_cub (the validate passes) or
+// ensure_scan (one exclusive sum of these types); sort_pairs48 sizes it itself.
+template <class In, class Out>
+static int ensure_scan(Ctx* c, In in, Out out, uint64_t n) {
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n));
+  return ensure(c, B_CUB_TMP, tb + 256);
+}
+template <class In, class Out>
+static int scan_max(Ctx* c, In in, Out out, uint64_t n) {
+  size_t tb = c->bufs[B_CUB_TMP].n;
+  HIPCHK(hipcub::DeviceScan::InclusiveScan(P<void>(c, B_CUB_TMP), tb, in, out, hipcub::Max(), (int)n, c->stream));
+  LAUNCHED(c->stream, "hipcub");
+  return 0;
+}
+template <class In, class Out>
+static int scan_sum(Ctx* c, In in, Out out, uint64_t n, hipStream_t s = nullptr) {
+  if (!s) s = c->stream;
+  size_t tb = c->bufs[B_CUB_TMP].n;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(P<void>(c, B_CUB_TMP), tb, in, out, (int)n, s));
+  LAUNCHED(s, "hipcub");
+  return 0;
+}
+// ... and its total (the last prefix + the last term, n >= 1) read back with
+// one wait, which up to three more reads share
+template <class T, class U>
+static int scan_sum_total(Ctx* c, T* in, U* out, uint64_t n, hipStream_t s, uint64_t* total, SmallRead r1 = {},
+                          SmallRead r2 = {}, SmallRead r3 = {}) {
+  if (!s) s = c->stream;
+  TRY(scan_sum(c, in, out, n, s));
+  U prefix{};
+  typename std::remove_const<T>::type term{};
+  TRY(read_small(c, s, {rd(out + n - 1, &prefix), rd(in + n - 1, &term), r1, r2, r3}));
+  *total = (uint64_t)prefix + term;
+  return 0;
+}
+// pairs sorted by the low 48 bits of their keys
+static int sort_pairs48(Ctx* c, const uint64_t* kin, uint64_t* kout, const uint64_t* vin, uint64_t* vout, uint64_t n) {
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, 48, c->stream));
+  TRY(ensure(c, B_CUB_TMP, tb + 256));
+  tb = c->bufs[B_CUB_TMP].n;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(P<void>(c, B_CUB_TMP), tb, kin, kout, vin, vout, (int)n, 0, 48, c->stream));
+  LAUNCHED(c->stream, "hipcub");
   return 0;
 }
 

@@ -4,8 +4,7 @@
 
 // global-table KeyIndexer::build workspace (full pass / skewed-bucket fallback)
 static int alloc_hash(Ctx* c, uint64_t n) {
-  uint64_t hc = 64;
-  while (hc < 2 * n) hc <<= 1;
+  const uint64_t hc = table_capacity(n);
   TRY(ensure(c, B_HKEYS, hc * 8));
   TRY(ensure(c, B_HVALS, hc * 8));
   TRY(ensure(c, B_LATEST, (n + 1) * 4));
@@ -23,8 +22,7 @@ static int index_global(Ctx* c, uint64_t n, uint64_t* n_index, const uint64_t* k
   TRY(alloc_hash(c, n));
   if (!okey) { okey = P<uint64_t>(c, B_IKEY); opacked = P<uint64_t>(c, B_IPACKED); }
   uint64_t* cnt = P<uint64_t>(c, B_COUNTERS);
-  uint64_t hc = 64;
-  while (hc < 2 * n) hc <<= 1;
+  const uint64_t hc = table_capacity(n);
   HIPCHK(hipMemsetAsync(P<void>(c, B_HKEYS), 0xff, hc * 8, c->stream));
   HIPCHK(hipMemsetAsync(P<void>(c, B_HVALS), 0, hc * 8, c->stream));
   HIPCHK(hipMemsetAsync(cnt + 7, 0, 8, c->stream));
@@ -32,23 +30,20 @@ static int index_global(Ctx* c, uint64_t n, uint64_t* n_index, const uint64_t* k
   if (n) {
     index_insert_kernel<<<blocks(n, 256), 256, 0, c->stream>>>(
         kh, mo, n, P<uint64_t>(c, B_HKEYS), P<unsigned long long>(c, B_HVALS), hc - 1, (unsigned long long*)(cnt + 7));
-    KCHK(c, "index_insert_kernel");
+    LAUNCHED(c->stream, "index_insert_kernel");
     index_latest_kernel<<<blocks(n, 256), 256, 0, c->stream>>>(
         kh, mo, n, P<uint64_t>(c, B_HKEYS), P<unsigned long long>(c, B_HVALS), hc - 1, (unsigned long long*)(cnt + 7),
         P<uint32_t>(c, B_LATEST));
-    KCHK(c, "index_latest_kernel");
-    HIPCHK(hipGetLastError());
+    LAUNCHED(c->stream, "index_latest_kernel");
   }
   TRY(scan_sum(c, P<uint32_t>(c, B_LATEST), P<uint32_t>(c, B_IPOS), n + 1));
   if (n) {
     index_emit_kernel<<<blocks(n, 256), 256, 0, c->stream>>>(kh, mo, P<uint32_t>(c, B_LATEST), P<uint32_t>(c, B_IPOS),
                                                              n, okey, opacked);
-    KCHK(c, "index_emit_kernel");
-    HIPCHK(hipGetLastError());
+    LAUNCHED(c->stream, "index_emit_kernel");
   }
   uint32_t nidx = 0;
-  HIPCHK(hipMemcpyAsync(&nidx, P<uint32_t>(c, B_IPOS) + n, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(spin_sync(c->stream));
+  TRY(read_small(c, c->stream, {rd(P<uint32_t>(c, B_IPOS) + n, &nidx)}));
   *n_index = nidx;
   return 0;
 }
@@ -124,15 +119,14 @@ static int launch_index_bucketed(Ctx* c, const uint64_t* kh, const uint64_t* mo,
     uint32_t* zw = index_zero_words(c, log2_nbk, &nz);
     if (!zeroed) HIPCHK(hipMemsetAsync(zw, 0, (size_t)nz * 4, c->stream));
     idx_hist_scatter_kernel<<<IDX_HBLOCKS, 256, nbk * 4, c->stream>>>(ia);
-    KCHK(c, "idx_hist_scatter_kernel");
+    LAUNCHED(c->stream, "idx_hist_scatter_kernel");
   }
   FinArgs fs{};  // n_slow == nullptr: no slow list
   if (slow) fs = *slow;
   idx_dedup_kernel<<<nbk, 512, 0, c->stream>>>(ia, fs);
-  KCHK(c, "idx_dedup_kernel");
+  LAUNCHED(c->stream, "idx_dedup_kernel");
   idx_emit_kernel<<<GLUE_BLOCKS, GLUE_THREADS, 0, c->stream>>>(ia);
-  KCHK(c, "idx_emit_kernel");
-  HIPCHK(hipGetLastError());
+  LAUNCHED(c->stream, "idx_emit_kernel");
   return 0;
 }
 
@@ -159,13 +153,12 @@ static int partition_impl(Ctx* c, const uint64_t* keys, const uint64_t* vals, ui
   a.out_v = out_v;
   a.counts = (uint64_t*)(P<uint32_t>(c, B_POFF) + ((nc + 1) & ~1ull));
   part_count_kernel<<<GLUE_BLOCKS, 256, 0, c->stream>>>(a);
-  KCHK(c, "part_count_kernel");
+  LAUNCHED(c->stream, "part_count_kernel");
   TRY(scan_sum(c, a.cnt, a.off, nc));
   part_scatter_kernel<<<GLUE_BLOCKS, 256, 0, c->stream>>>(a);
-  KCHK(c, "part_scatter_kernel");
+  LAUNCHED(c->stream, "part_scatter_kernel");
   part_counts_kernel<<<1, 64, 0, c->stream>>>(a);
-  KCHK(c, "part_counts_kernel");
-  HIPCHK(hipGetLastError());
+  LAUNCHED(c->stream, "part_counts_kernel");
   if (d_counts) *d_counts = a.counts;
   if (counts) {
     HIPCHK(hipMemcpyAsync(counts, a.counts, world * 8, hipMemcpyDeviceToHost, c->stream));
@@ -205,10 +198,10 @@ static int index_build_sep(Ctx* c, const uint64_t* keys, const uint64_t* vals, u
   uint32_t* zw = index_zero_words(c, log2_nbk, &nz);
   if (d_n) {
     index_prep_dev_kernel<<<(std::max<uint32_t>(nz, 64) + 255) / 256, 256, 0, c->stream>>>(pl, d_n, zw, nz);
-    KCHK(c, "index_prep_dev_kernel");
+    LAUNCHED(c->stream, "index_prep_dev_kernel");
   } else {
     index_prep_kernel<<<(nz + 255) / 256, 256, 0, c->stream>>>(pl, n, zw, nz);
-    KCHK(c, "index_prep_kernel");
+    LAUNCHED(c->stream, "index_prep_kernel");
   }
   TRY(launch_index_bucketed(c, keys, vals, &pl->n_chain, &pl->status, log2_nbk, okeys, opacked, pl, false, nullptr,
                             true));
@@ -230,8 +223,7 @@ extern "C" int srd_index_build_device(srd_ctx* c, const uint64_t* d_pairs, uint6
   TRY(ensure(c, B_MVAL, n * 8));
   deinterleave_kernel<<<blocks(std::min<uint64_t>(n, 1 << 20), 256), 256, 0, c->stream>>>(
       d_pairs, n, P<uint64_t>(c, B_MKEY), P<uint64_t>(c, B_MVAL));
-  KCHK(c, "deinterleave_kernel");
-  HIPCHK(hipGetLastError());
+  LAUNCHED(c->stream, "deinterleave_kernel");
   return index_build_sep(c, P<uint64_t>(c, B_MKEY), P<uint64_t>(c, B_MVAL), n, d_out_keys, d_out_packed, n_index);
 }
 
@@ -239,8 +231,8 @@ extern "C" int srd_index_hash_device(srd_ctx* c, const uint64_t* d_keys, uint64_
   if (!c || (n && (!d_keys || !d_out))) { set_err("bad argument"); return SRD_ERR_ARG; }
   if (!n) return 0;
   HIPCHK(hipSetDevice(c->device));
-  index_hash_kernel<<<(unsigned)std::min<uint64_t>((n + 255) / 256, 8192), 256, 0,
-                      stream ? (hipStream_t)stream : c->stream>>>(d_keys, n, d_out);
-  HIPCHK(hipGetLastError());
+  hipStream_t s = stream_of(c, stream);
+  index_hash_kernel<<<(unsigned)std::min<uint64_t>((n + 255) / 256, 8192), 256, 0, s>>>(d_keys, n, d_out);
+  LAUNCHED(s, "index_hash_kernel");
   return 0;
 }

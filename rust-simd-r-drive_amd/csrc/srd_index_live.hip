@@ -7,10 +7,7 @@
 //   KeyIndexer::insert / remove src/storage_engine/key_indexer.rs:135-160, :174-178
 //   batch_delete_key_hashes     src/storage_engine/data_store.rs:995-1024
 //
-// Slot states (the word in packed[]): TBL_EMPTY (never used: a probe ends
-// here), live (tag16 << 48 | offset48), TBL_DELETED (the slot keeps its key,
-// the key is absent: a probe goes on past it, an insert of the same key
-// revives it).  A slot never returns to TBL_EMPTY, so no probe chain breaks.
+// The slot states and the probe / claim loops are srd_table.h.
 //
 // An apply is three launches, each race-free by what it may touch:
 //   1 live_dedupe_kernel  batch -> scratch table of batch positions (table untouched)
@@ -34,9 +31,7 @@ struct LiveArgs {
   uint32_t* dtomb;      // [2^log2dc / 32] bit s: a pair of slot s's key is a tombstone (deleted_keys, data_store.rs:861,896)
   uint32_t log2dc;
   uint32_t* lslot;      // [n] the scratch slot of pair i's key
-  uint64_t* tkeys;      // the table
-  uint64_t* tpacked;
-  uint32_t log2cap;
+  Table t;              // the table
   uint64_t* op_slot;    // [n] table slot to store op_val into / LIVE_OP_CLAIM / LIVE_OP_NONE
   uint64_t* op_val;     // [n]
   unsigned long long* cnt;  // [4] inserted, updated, removed (per distinct key), new slots needed
@@ -84,7 +79,6 @@ __global__ void live_dedupe_kernel(LiveArgs a) {
 // packed value's tag with the new one's; both are key_hash >> 48 of the same
 // key_hash, so it can never fire here and there is no error path for it.
 __global__ void live_lookup_kernel(LiveArgs a) {
-  const uint64_t mask = (1ull << a.log2cap) - 1;
   unsigned long long ins = 0, upd = 0, rem = 0, fresh = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (uint64_t)gridDim.x * blockDim.x) {
     uint64_t op = LIVE_OP_NONE, val = 0;
@@ -93,14 +87,9 @@ __global__ void live_lookup_kernel(LiveArgs a) {
       const uint64_t k = a.kh[i];
       const bool del = (a.dtomb[ds >> 5] >> (ds & 31)) & 1;
       const uint64_t np = (k >> 48 << 48) | (a.mo[i] & 0xFFFFFFFFFFFFull);  // KeyIndexer::pack(tag_from_hash, offset)
-      uint64_t s = idx_slot(k, a.log2cap), p;
-      bool found = false;
-      for (;;) {  // terminates: at most cap/2 slots are not empty
-        p = a.tpacked[s];
-        if (p == TBL_EMPTY) break;
-        if (a.tkeys[s] == k) { found = true; break; }
-        s = (s + 1) & mask;
-      }
+      uint64_t s;
+      const uint64_t p = table_find(a.t, k, &s);
+      const bool found = p != TBL_EMPTY;
       const bool present = found && p != TBL_DELETED;
       if (del) {
         if (present) { op = s; val = TBL_DELETED; rem++; }
@@ -142,25 +131,16 @@ __global__ void live_lookup_kernel(LiveArgs a) {
 // contend for a slot: the CAS only succeeds on TBL_EMPTY.  Readers come in a
 // later launch and see both words.
 __global__ void live_commit_kernel(LiveArgs a) {
-  const uint64_t mask = (1ull << a.log2cap) - 1;
+  const uint64_t mask = (1ull << a.t.log2cap) - 1;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t op = a.op_slot[i];
     if (op == LIVE_OP_NONE) continue;
     const uint64_t val = a.op_val[i];
     if (op != LIVE_OP_CLAIM) {
-      a.tpacked[op & mask] = val;
+      a.t.packed[op & mask] = val;
       continue;
     }
-    const uint64_t k = a.kh[i];
-    uint64_t s = idx_slot(k, a.log2cap);
-    for (;;) {  // terminates: the host admitted the batch only if used + new <= cap/2
-      if (atomicCAS((unsigned long long*)a.tpacked + s, (unsigned long long)TBL_EMPTY, (unsigned long long)val) ==
-          TBL_EMPTY) {
-        a.tkeys[s] = k;
-        break;
-      }
-      s = (s + 1) & mask;
-    }
+    table_claim(a.t, a.kh[i], val);  // terminates: the host admitted the batch (table_admits)
   }
 }
 
@@ -190,10 +170,9 @@ __global__ void live_gather_kernel(const uint64_t* tkeys, const uint64_t* tpacke
 
 // batch_delete_key_hashes keeps the hashes the index holds (data_store.rs:
 // 1004-1008), in input order, duplicates included
-__global__ void live_present_kernel(const uint64_t* tkeys, const uint64_t* tpacked, uint32_t log2cap, const uint64_t* q,
-                                    uint64_t n, uint32_t* flag) {
+__global__ void live_present_kernel(Table t, const uint64_t* q, uint64_t n, uint32_t* flag) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-    flag[i] = idx_get_packed(tkeys, tpacked, log2cap, q[i]) != TBL_EMPTY;
+    flag[i] = table_get(t, q[i]) != TBL_EMPTY;
 }
 
 // ... and appends one tombstone per kept hash from `tail`: a NULL byte and

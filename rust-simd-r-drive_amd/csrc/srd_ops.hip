@@ -2,29 +2,43 @@
 // by srd_api.hip): stream probe, batch digests, synth, batch writer, device
 // lookup table, batched reads and the table's maintenance, iterator and
 // compaction.
+
+// A device allocation / an event that lasts for one call, released on every return path
+// (no workspace buffer: as large as the caller's input, the context would keep and report it)
+struct DevTmp {
+  void* p = nullptr;
+  DevTmp() = default;
+  DevTmp(const DevTmp&) = delete;
+  ~DevTmp() { if (p) hipFree(p); }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+};
+struct EventTmp {
+  hipEvent_t e = nullptr;
+  EventTmp() = default;
+  EventTmp(const EventTmp&) = delete;
+  ~EventTmp() { if (e) hipEventDestroy(e); }
+};
+
 extern "C" int srd_stream_probe_device(srd_ctx* c, const uint8_t* d_buf, uint64_t bytes, int reps, double* best_ms,
                                        double* median_ms) {
   if (!c || !d_buf || bytes < TILE || reps < 1 || !best_ms) { set_err("bad argument"); return SRD_ERR_ARG; }
   HIPCHK(hipSetDevice(c->device));
   const uint64_t ntiles = bytes / TILE;
   TRY(ensure(c, B_PROBE, (uint64_t)c->scan_blocks * 16 * 4));
-  hipEvent_t e[2];
-  for (auto& x : e) HIPCHK(hipEventCreateWithFlags(&x, hipEventReleaseToDevice));
+  EventTmp e[2];
+  for (auto& x : e) HIPCHK(hipEventCreateWithFlags(&x.e, hipEventReleaseToDevice));
   std::vector<float> ms;
-  int rc = 0;
-  for (int r = 0; r < reps + 1 && !rc; r++) {  // (the first run warms the code and the TLB)
-    hipExtLaunchKernelGGL(stream_probe_kernel, dim3(c->scan_blocks), dim3(1024), 0, c->stream, e[0], e[1], 0, d_buf,
-                          ntiles, P<uint32_t>(c, B_PROBE));
+  for (int r = 0; r < reps + 1; r++) {  // (the first run warms the code and the TLB)
+    hipExtLaunchKernelGGL(stream_probe_kernel, dim3(c->scan_blocks), dim3(1024), 0, c->stream, e[0].e, e[1].e, 0,
+                          d_buf, ntiles, P<uint32_t>(c, B_PROBE));
     float t = 0;
-    if (hipGetLastError() != hipSuccess || hipEventSynchronize(e[1]) != hipSuccess ||
-        hipEventElapsedTime(&t, e[0], e[1]) != hipSuccess) {
+    if (hipGetLastError() != hipSuccess || hipEventSynchronize(e[1].e) != hipSuccess ||
+        hipEventElapsedTime(&t, e[0].e, e[1].e) != hipSuccess) {
       set_err("stream probe launch failed");
-      rc = SRD_ERR_HIP;
+      return SRD_ERR_HIP;
     }
     if (r) ms.push_back(t);
   }
-  for (auto& x : e) hipEventDestroy(x);
-  if (rc) return rc;
   std::sort(ms.begin(), ms.end());
   *best_ms = ms[0];
   if (median_ms) *median_ms = ms[ms.size() / 2];
@@ -34,22 +48,20 @@ extern "C" int srd_stream_probe_device(srd_ctx* c, const uint8_t* d_buf, uint64_
 extern "C" int srd_crc32_batch_device(srd_ctx* c, const uint8_t* d_buf, const uint64_t* d_offs,
                                       const uint64_t* d_lens, uint64_t n, uint32_t* d_out, void* stream) {
   if (!c) { set_err("bad argument"); return SRD_ERR_ARG; }
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t s = stream_of(c, stream);
   if (!n) return 0;
   crc_batch_kernel<<<(unsigned)std::min<uint64_t>(n, 8192), 64, 0, s>>>(d_buf, d_offs, d_lens, n, d_out);
-  KCHK(c, "crc_batch_kernel");
-  HIPCHK(hipGetLastError());
+  LAUNCHED(s, "crc_batch_kernel");
   return 0;
 }
 
 extern "C" int srd_xxh3_64_batch_device(srd_ctx* c, const uint8_t* d_keys, const uint64_t* d_offs,
                                         const uint64_t* d_lens, uint64_t n, uint64_t* d_out, void* stream) {
   if (!c) { set_err("bad argument"); return SRD_ERR_ARG; }
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t s = stream_of(c, stream);
   if (!n) return 0;
   xxh3_batch_kernel<<<blocks(n, 256), 256, 0, s>>>(d_keys, d_offs, d_lens, n, d_out);
-  KCHK(c, "xxh3_batch_kernel");
-  HIPCHK(hipGetLastError());
+  LAUNCHED(s, "xxh3_batch_kernel");
   return 0;
 }
 
@@ -59,20 +71,19 @@ static int batch_host(srd_ctx* c, const uint8_t* buf, uint64_t blen, const uint6
   HIPCHK(hipSetDevice(c->device));
   for (uint64_t i = 0; i < n; i++)
     if (offs[i] > blen || lens[i] > blen - offs[i]) { set_err("range out of bounds"); return SRD_ERR_ARG; }
-  void *db = nullptr, *dof = nullptr, *dl = nullptr, *dout = nullptr;
-  HIPCHK(hipMalloc(&db, blen + 1));
-  HIPCHK(hipMalloc(&dof, n * 8 + 8));
-  HIPCHK(hipMalloc(&dl, n * 8 + 8));
-  HIPCHK(hipMalloc(&dout, n * sizeof(OUT) + 8));
-  if (blen) HIPCHK(hipMemcpyAsync(db, buf, blen, hipMemcpyHostToDevice, c->stream));
+  DevTmp db, dof, dl, dout;
+  HIPCHK(db.alloc(blen + 1));
+  HIPCHK(dof.alloc(n * 8 + 8));
+  HIPCHK(dl.alloc(n * 8 + 8));
+  HIPCHK(dout.alloc(n * sizeof(OUT) + 8));
+  if (blen) HIPCHK(hipMemcpyAsync(db.p, buf, blen, hipMemcpyHostToDevice, c->stream));
   if (n) {
-    HIPCHK(hipMemcpyAsync(dof, offs, n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dl, lens, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dof.p, offs, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dl.p, lens, n * 8, hipMemcpyHostToDevice, c->stream));
   }
-  int r = launch((const uint8_t*)db, (const uint64_t*)dof, (const uint64_t*)dl, (OUT*)dout);
-  if (!r && n) HIPCHK(hipMemcpyAsync(out, dout, n * sizeof(OUT), hipMemcpyDeviceToHost, c->stream));
+  int r = launch((const uint8_t*)db.p, (const uint64_t*)dof.p, (const uint64_t*)dl.p, (OUT*)dout.p);
+  if (!r && n) HIPCHK(hipMemcpyAsync(out, dout.p, n * sizeof(OUT), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(spin_sync(c->stream));
-  hipFree(db); hipFree(dof); hipFree(dl); hipFree(dout);
   return r;
 }
 
@@ -118,20 +129,17 @@ static int synth_launch(Ctx* c, uint8_t* d_abs, const std::vector<uint64_t>& off
   const uint64_t n = off.size();
   if (!n) return 0;
   HIPCHK(hipSetDevice(c->device));
-  void *doff = nullptr, *dl = nullptr;
-  HIPCHK(hipMalloc(&doff, n * 8));
-  HIPCHK(hipMemcpyAsync(doff, off.data(), n * 8, hipMemcpyHostToDevice, c->stream));
+  DevTmp doff, dl;
+  HIPCHK(doff.alloc(n * 8));
+  HIPCHK(hipMemcpyAsync(doff.p, off.data(), n * 8, hipMemcpyHostToDevice, c->stream));
   if (lens) {
-    HIPCHK(hipMalloc(&dl, n * 8));
-    HIPCHK(hipMemcpyAsync(dl, lens + e0, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(dl.alloc(n * 8));
+    HIPCHK(hipMemcpyAsync(dl.p, lens + e0, n * 8, hipMemcpyHostToDevice, c->stream));
   }
   synth_kernel<<<(unsigned)std::min<uint64_t>(n, 65536), 64, 0, c->stream>>>(
-      d_abs, (const uint64_t*)doff, (const uint64_t*)dl, fixed_len, n, seed, e0, clip_lo);
-  KCHK(c, "synth_kernel");
-  HIPCHK(hipGetLastError());
+      d_abs, (const uint64_t*)doff.p, (const uint64_t*)dl.p, fixed_len, n, seed, e0, clip_lo);
+  LAUNCHED(c->stream, "synth_kernel");
   HIPCHK(spin_sync(c->stream));
-  hipFree(doff);
-  if (dl) hipFree(dl);
   return 0;
 }
 
@@ -191,11 +199,7 @@ static int launch_write(Ctx* c, hipStream_t s, const uint8_t* pay, const uint8_t
   else
 #endif
     write_kernel<<<g, SCAN_WAVES_V2 * 64, 0, s>>>(w);
-  HIPCHK(hipGetLastError());
-  if (sync_debug()) {
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
-  }
+  LAUNCHED(s, "write_kernel");
   return 0;
 }
 
@@ -208,8 +212,7 @@ extern "C" int srd_batch_write_device(srd_ctx* c, const uint8_t* d_keys, const u
     return SRD_ERR_ARG;
   }
   HIPCHK(hipSetDevice(c->device));
-  return launch_write(c, stream ? (hipStream_t)stream : c->stream, d_payloads, d_keys, d_entries, n, d_out, out_base,
-                      d_kh_out, d_mo_out);
+  return launch_write(c, stream_of(c, stream), d_payloads, d_keys, d_entries, n, d_out, out_base, d_kh_out, d_mo_out);
 }
 
 extern "C" int srd_batch_write(srd_ctx* c, uint64_t tail, const uint8_t* keys, const uint64_t* key_offs,
@@ -287,17 +290,8 @@ extern "C" int srd_batch_write(srd_ctx* c, uint64_t tail, const uint8_t* keys, c
 }
 
 // ---------------------------------------------------------------------------
-// Device KeyIndexer table + batched keyed reads (srd_index.hip)
-static uint32_t table_log2cap(uint64_t table_bytes) {
-  uint32_t l = 0;
-  while (l < 62 && (16ull << (l + 1)) <= table_bytes) l++;
-  return l;
-}
-extern "C" uint64_t srd_index_table_bytes(uint64_t n) {
-  uint64_t cap = 64;
-  while (cap < 2 * n) cap <<= 1;
-  return 16 * cap;
-}
+// Device KeyIndexer table + batched keyed reads (srd_table.h, srd_index.hip)
+extern "C" uint64_t srd_index_table_bytes(uint64_t n) { return table_bytes_for(n); }
 static unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 8192)); }
 
 extern "C" int srd_index_table_build_device(srd_ctx* c, const uint64_t* d_keys, const uint64_t* d_packed, uint64_t n,
@@ -307,15 +301,10 @@ extern "C" int srd_index_table_build_device(srd_ctx* c, const uint64_t* d_keys, 
     return SRD_ERR_ARG;
   }
   HIPCHK(hipSetDevice(c->device));
-  const uint32_t l = table_log2cap(table_bytes);
-  uint64_t* tk = (uint64_t*)d_table;
-  uint64_t* tp = tk + (1ull << l);
-  HIPCHK(hipMemsetAsync(tp, 0xFF, (1ull << l) * 8, c->stream));
-  if (n) {
-    idx_table_insert_kernel<<<grid_for(n), 256, 0, c->stream>>>(d_keys, d_packed, n, tk, (unsigned long long*)tp, l);
-    KCHK(c, "idx_table_insert_kernel");
-    HIPCHK(hipGetLastError());
-  }
+  const Table t = table_view(d_table, table_bytes);
+  HIPCHK(hipMemsetAsync(t.packed, 0xFF, (1ull << t.log2cap) * 8, c->stream));
+  if (n) idx_table_insert_kernel<<<grid_for(n), 256, 0, c->stream>>>(d_keys, d_packed, n, t);
+  LAUNCHED(c->stream, "idx_table_insert_kernel");
   HIPCHK(spin_sync(c->stream));
   return 0;
 }
@@ -323,17 +312,15 @@ extern "C" int srd_index_table_build_device(srd_ctx* c, const uint64_t* d_keys, 
 extern "C" int srd_index_get_packed_device(srd_ctx* c, const void* d_table, uint64_t table_bytes,
                                            const uint64_t* d_hashes, uint64_t n, uint64_t* d_packed_out,
                                            void* stream) {
-  if (!c || !d_table || table_bytes < 16 * 64 || (n && (!d_hashes || !d_packed_out))) {
+  if (!c || !table_ok(d_table, table_bytes) || (n && (!d_hashes || !d_packed_out))) {
     set_err("bad argument");
     return SRD_ERR_ARG;
   }
   if (!n) return 0;
   HIPCHK(hipSetDevice(c->device));
-  const uint32_t l = table_log2cap(table_bytes);
-  const uint64_t* tk = (const uint64_t*)d_table;
-  idx_get_packed_kernel<<<grid_for(n), 256, 0, stream ? (hipStream_t)stream : c->stream>>>(tk, tk + (1ull << l), l,
-                                                                                             d_hashes, n, d_packed_out);
-  HIPCHK(hipGetLastError());
+  hipStream_t s = stream_of(c, stream);
+  idx_get_packed_kernel<<<grid_for(n), 256, 0, s>>>(table_view(d_table, table_bytes), d_hashes, n, d_packed_out);
+  LAUNCHED(s, "idx_get_packed_kernel");
   return 0;
 }
 
@@ -341,17 +328,16 @@ extern "C" int srd_batch_read_hashed_device(srd_ctx* c, const void* d_table, uin
                                             const uint8_t* d_file, uint64_t flen, const uint64_t* d_hashes,
                                             const uint64_t* d_verify, uint64_t n, uint64_t* d_start, uint64_t* d_end,
                                             void* stream) {
-  if (!c || !d_table || table_bytes < 16 * 64 || (n && (!d_hashes || !d_start || !d_end || (flen && !d_file)))) {
+  if (!c || !table_ok(d_table, table_bytes) || (n && (!d_hashes || !d_start || !d_end || (flen && !d_file)))) {
     set_err("bad argument");
     return SRD_ERR_ARG;
   }
   if (!n) return 0;
   HIPCHK(hipSetDevice(c->device));
-  const uint32_t l = table_log2cap(table_bytes);
-  const uint64_t* tk = (const uint64_t*)d_table;
-  batch_read_kernel<<<grid_for(n), 256, 0, stream ? (hipStream_t)stream : c->stream>>>(
-      tk, tk + (1ull << l), l, d_file, flen, d_hashes, d_verify, n, d_start, d_end);
-  HIPCHK(hipGetLastError());
+  hipStream_t s = stream_of(c, stream);
+  batch_read_kernel<<<grid_for(n), 256, 0, s>>>(table_view(d_table, table_bytes), d_file, flen, d_hashes, d_verify, n,
+                                                d_start, d_end);
+  LAUNCHED(s, "batch_read_kernel");
   return 0;
 }
 
@@ -366,35 +352,30 @@ extern "C" int srd_batch_read(srd_ctx* c, const void* d_table, uint64_t table_by
   HIPCHK(hipSetDevice(c->device));
   uint64_t klen = 0;
   for (uint64_t i = 0; i < n; i++) klen = std::max(klen, key_offs[i] + key_lens[i]);
-  void *dk = nullptr, *dof = nullptr, *dl = nullptr, *dh = nullptr, *ds = nullptr, *de = nullptr;
-  int r = 0;
-  auto cleanup = [&] { hipFree(dk); hipFree(dof); hipFree(dl); hipFree(dh); hipFree(ds); hipFree(de); };
-  if (hipMalloc(&dk, klen + 1) || hipMalloc(&dof, n * 8) || hipMalloc(&dl, n * 8) || hipMalloc(&dh, n * 8) ||
-      hipMalloc(&ds, n * 8) || hipMalloc(&de, n * 8)) {
-    cleanup();
+  DevTmp dk, dof, dl, dh, ds, de;
+  if (dk.alloc(klen + 1) || dof.alloc(n * 8) || dl.alloc(n * 8) || dh.alloc(n * 8) || ds.alloc(n * 8) ||
+      de.alloc(n * 8)) {
     set_err("hipMalloc failed");
     return SRD_ERR_ALLOC;
   }
-  if (klen) HIPCHK(hipMemcpyAsync(dk, keys, klen, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dof, key_offs, n * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dl, key_lens, n * 8, hipMemcpyHostToDevice, c->stream));
-  r = srd_xxh3_64_batch_device(c, (const uint8_t*)dk, (const uint64_t*)dof, (const uint64_t*)dl, n, (uint64_t*)dh,
-                               nullptr);  // compute_hash_batch (data_store.rs:1112)
+  if (klen) HIPCHK(hipMemcpyAsync(dk.p, keys, klen, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dof.p, key_offs, n * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dl.p, key_lens, n * 8, hipMemcpyHostToDevice, c->stream));
+  int r = srd_xxh3_64_batch_device(c, (const uint8_t*)dk.p, (const uint64_t*)dof.p, (const uint64_t*)dl.p, n,
+                                   (uint64_t*)dh.p, nullptr);  // compute_hash_batch (data_store.rs:1112)
   // batch_read verifies every key by its own tag (Some(keys), :1113)
-  if (!r) r = srd_batch_read_hashed_device(c, d_table, table_bytes, d_file, flen, (const uint64_t*)dh,
-                                           (const uint64_t*)dh, n, (uint64_t*)ds, (uint64_t*)de, nullptr);
+  if (!r) r = srd_batch_read_hashed_device(c, d_table, table_bytes, d_file, flen, (const uint64_t*)dh.p,
+                                           (const uint64_t*)dh.p, n, (uint64_t*)ds.p, (uint64_t*)de.p, nullptr);
   if (!r) {
-    HIPCHK(hipMemcpyAsync(start_out, ds, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(end_out, de, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(start_out, ds.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(end_out, de.p, n * 8, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(spin_sync(c->stream));
-  cleanup();
   return r;
 }
 
 // ---------------------------------------------------------------------------
 // The table kept live (srd_index_live.hip): reindex, export, batched delete
-static bool table_ok(const void* d_table, uint64_t table_bytes) { return d_table && table_bytes >= 16 * 64; }
 
 // reindex (data_store.rs:224-259) of n pairs on stream s: dedupe and look up
 // (the table is only read), one host wait for the counts, then the commit.
@@ -423,9 +404,7 @@ static int apply_impl(Ctx* c, void* d_table, uint64_t table_bytes, uint64_t* use
   a.dtomb = P<uint32_t>(c, B_LV_DTOMB);
   a.log2dc = log2dc;
   a.lslot = P<uint32_t>(c, B_LV_LSLOT);
-  a.log2cap = table_log2cap(table_bytes);
-  a.tkeys = (uint64_t*)d_table;
-  a.tpacked = a.tkeys + (1ull << a.log2cap);
+  a.t = table_view(d_table, table_bytes);
   a.op_slot = P<uint64_t>(c, B_LV_OPS);
   a.op_val = P<uint64_t>(c, B_LV_OPV);
   a.cnt = P<unsigned long long>(c, B_LV_CNT);
@@ -433,23 +412,20 @@ static int apply_impl(Ctx* c, void* d_table, uint64_t table_bytes, uint64_t* use
   HIPCHK(hipMemsetAsync(a.dtomb, 0, dc / 32 * 4, s));
   HIPCHK(hipMemsetAsync(a.cnt, 0, 32, s));
   live_dedupe_kernel<<<grid_for(n), 256, 0, s>>>(a);
+  LAUNCHED(s, "live_dedupe_kernel");
   live_lookup_kernel<<<grid_for(n), 256, 0, s>>>(a);
-  HIPCHK(hipGetLastError());
-  uint64_t* h = c->h_small + 16;
-  HIPCHK(hipMemcpyAsync(h, a.cnt, 32, hipMemcpyDeviceToHost, s));
-  HIPCHK(spin_sync(s));
-  const uint64_t ins = h[0], upd = h[1], rem = h[2], fresh = h[3];
-  if (*used + fresh > (1ull << a.log2cap) / 2) {
-    set_err("index table full: " + std::to_string(*used) + " used slots + " + std::to_string(fresh) +
-            " new keys exceed half of " + std::to_string(1ull << a.log2cap));
+  LAUNCHED(s, "live_lookup_kernel");
+  struct { unsigned long long ins, upd, rem, fresh; } h;
+  TRY(read_small(c, s, {SmallRead{a.cnt, &h, sizeof h}}));
+  if (!table_admits(*used, h.fresh, a.t.log2cap)) {
+    set_err("index table full: " + std::to_string(*used) + " used slots + " + std::to_string(h.fresh) +
+            " new keys exceed half of " + std::to_string(1ull << a.t.log2cap));
     return SRD_ERR_FULL;
   }
-  if (ins + upd + rem) {
-    live_commit_kernel<<<grid_for(n), 256, 0, s>>>(a);
-    HIPCHK(hipGetLastError());
-  }
-  *used += fresh;
-  if (stats) *stats = srd_index_apply_stats{ins, upd, rem};
+  if (h.ins + h.upd + h.rem) live_commit_kernel<<<grid_for(n), 256, 0, s>>>(a);
+  LAUNCHED(s, "live_commit_kernel");
+  *used += h.fresh;
+  if (stats) *stats = srd_index_apply_stats{h.ins, h.upd, h.rem};
   return 0;
 }
 
@@ -461,8 +437,7 @@ extern "C" int srd_index_table_apply_device(srd_ctx* c, void* d_table, uint64_t 
     set_err("bad argument");
     return SRD_ERR_ARG;
   }
-  return apply_impl(c, d_table, table_bytes, used, d_key_hashes, d_meta_offs, d_tomb, n, stats,
-                    stream ? (hipStream_t)stream : c->stream);
+  return apply_impl(c, d_table, table_bytes, used, d_key_hashes, d_meta_offs, d_tomb, n, stats, stream_of(c, stream));
 }
 
 extern "C" int srd_index_table_export_device(srd_ctx* c, const void* d_table, uint64_t table_bytes,
@@ -473,18 +448,15 @@ extern "C" int srd_index_table_export_device(srd_ctx* c, const void* d_table, ui
     return SRD_ERR_ARG;
   }
   HIPCHK(hipSetDevice(c->device));
-  const uint32_t l = table_log2cap(table_bytes);
-  const uint64_t cap = 1ull << l;
-  const uint64_t* tk = (const uint64_t*)d_table;
+  const Table t = table_view(d_table, table_bytes);
+  const uint64_t cap = 1ull << t.log2cap;
   TRY(ensure(c, B_LV_CNT, 64));
   unsigned long long* cnt = P<unsigned long long>(c, B_LV_CNT) + 4;
-  uint64_t* h = c->h_small + 16;
   HIPCHK(hipMemsetAsync(cnt, 0, 8, c->stream));
-  live_count_kernel<<<grid_for(cap), 256, 0, c->stream>>>(tk + cap, cap, cnt);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(h, cnt, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(spin_sync(c->stream));
-  const uint64_t nl = h[0];
+  live_count_kernel<<<grid_for(cap), 256, 0, c->stream>>>(t.packed, cap, cnt);
+  LAUNCHED(c->stream, "live_count_kernel");
+  unsigned long long nl = 0;
+  TRY(read_small(c, c->stream, {rd(cnt, &nl)}));
   *n_live = nl;
   if (!d_keys_out || !nl) return 0;
   if (nl > cap_out) { set_err("cap_out too small for the live pairs"); return SRD_ERR_ARG; }
@@ -494,20 +466,11 @@ extern "C" int srd_index_table_export_device(srd_ctx* c, const void* d_table, ui
   // whatever order the gather's atomic counter handed out
   TRY(ensure(c, B_LV_XK, nl * 8));
   TRY(ensure(c, B_LV_XP, nl * 8));
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                            (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)nl, 0, 48, c->stream));
-  TRY(ensure(c, B_CUB_TMP, tb + 256));
   HIPCHK(hipMemsetAsync(cnt, 0, 8, c->stream));
-  live_gather_kernel<<<grid_for(cap), 256, 0, c->stream>>>(tk, tk + cap, cap, cnt, P<uint64_t>(c, B_LV_XK),
+  live_gather_kernel<<<grid_for(cap), 256, 0, c->stream>>>(t.keys, t.packed, cap, cnt, P<uint64_t>(c, B_LV_XK),
                                                           P<uint64_t>(c, B_LV_XP), nl);
-  KCHK(c, "live_gather_kernel");
-  tb = c->bufs[B_CUB_TMP].n;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(P<void>(c, B_CUB_TMP), tb, (const uint64_t*)P<uint64_t>(c, B_LV_XP),
-                                            d_packed_out, (const uint64_t*)P<uint64_t>(c, B_LV_XK), d_keys_out,
-                                            (int)nl, 0, 48, c->stream));
-  KCHK(c, "hipcub");
-  HIPCHK(hipGetLastError());
+  LAUNCHED(c->stream, "live_gather_kernel");
+  TRY(sort_pairs48(c, P<uint64_t>(c, B_LV_XP), d_packed_out, P<uint64_t>(c, B_LV_XK), d_keys_out, nl));
   HIPCHK(spin_sync(c->stream));
   return 0;
 }
@@ -524,21 +487,15 @@ extern "C" int srd_batch_delete_hashed_device(srd_ctx* c, void* d_table, uint64_
   if (n_deleted) *n_deleted = 0;
   if (!n) return 0;
   HIPCHK(hipSetDevice(c->device));
-  const uint32_t l = table_log2cap(table_bytes);
-  const uint64_t* tk = (const uint64_t*)d_table;
   TRY(ensure(c, B_LV_FLAG, n * 4));
   TRY(ensure(c, B_LV_POS, n * 4));
-  TRY(ensure_cub(c, n));
   uint32_t* flag = P<uint32_t>(c, B_LV_FLAG);
   uint32_t* pos = P<uint32_t>(c, B_LV_POS);
-  live_present_kernel<<<grid_for(n), 256, 0, c->stream>>>(tk, tk + (1ull << l), l, d_hashes, n, flag);
-  KCHK(c, "live_present_kernel");
-  TRY(scan_sum(c, flag, pos, n));
-  uint32_t* h = (uint32_t*)(c->h_small + 20);
-  HIPCHK(hipMemcpyAsync(h, pos + n - 1, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(h + 1, flag + n - 1, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(spin_sync(c->stream));
-  const uint64_t nk = (uint64_t)h[0] + h[1];
+  TRY(ensure_scan(c, flag, pos, n));
+  live_present_kernel<<<grid_for(n), 256, 0, c->stream>>>(table_view(d_table, table_bytes), d_hashes, n, flag);
+  LAUNCHED(c->stream, "live_present_kernel");
+  uint64_t nk = 0;
+  TRY(scan_sum_total(c, flag, pos, n, c->stream, &nk));
   if (!nk) return 0;  // (the reference returns the unchanged tail: data_store.rs:1011-1014)
   const uint64_t nt = tail + 21 * nk;
   if (srd_padded_size(nt) > file_cap) { set_err("file_cap too small for the tombstones"); return SRD_ERR_ARG; }
@@ -548,7 +505,7 @@ extern "C" int srd_batch_delete_hashed_device(srd_ctx* c, void* d_table, uint64_
   TRY(ensure(c, B_WMO, nk * 8));
   live_tomb_entries_kernel<<<grid_for(n), 256, 0, c->stream>>>(d_hashes, flag, pos, n, tail,
                                                               P<srd_write_entry>(c, B_LV_ENT));
-  KCHK(c, "live_tomb_entries_kernel");
+  LAUNCHED(c->stream, "live_tomb_entries_kernel");
   HIPCHK(hipMemsetAsync(P<void>(c, B_LV_TOMB), 1, nk, c->stream));
   // (a tombstone reads no payload or key bytes: d_file only stands for the payload base)
   TRY(launch_write(c, c->stream, d_file, nullptr, P<srd_write_entry>(c, B_LV_ENT), nk, d_file, 0,
@@ -578,27 +535,21 @@ static int iter_run(Ctx* c, const uint8_t* d_file, uint64_t flen, const uint64_t
   TRY(ensure(c, B_IT_ST, n * 8));
   TRY(ensure(c, B_IT_EN, n * 8));
   TRY(ensure(c, B_IT_KEPT, 64));
-  TRY(ensure_cub(c, n));
   uint32_t* flag = P<uint32_t>(c, B_IT_FLAG);
   uint32_t* pos = P<uint32_t>(c, B_IT_POS);
+  TRY(ensure_scan(c, flag, pos, n));
   unsigned long long* kept = P<unsigned long long>(c, B_IT_KEPT);
   HIPCHK(hipMemsetAsync(kept, 0, 8, c->stream));
   iter_flag_kernel<<<grid_for(n), 256, 0, c->stream>>>(d_file, flen, d_packed, n, flag, P<uint64_t>(c, B_IT_ST),
                                                        P<uint64_t>(c, B_IT_EN), kept);
-  KCHK(c, "iter_flag_kernel");
-  TRY(scan_sum(c, flag, pos, n));
-  uint32_t last[2] = {0, 0};
+  LAUNCHED(c->stream, "iter_flag_kernel");
+  uint64_t nv = 0;
   unsigned long long hk = 0;
-  HIPCHK(hipMemcpyAsync(&last[0], pos + n - 1, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(&last[1], flag + n - 1, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(&hk, kept, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(spin_sync(c->stream));
-  const uint64_t nv = (uint64_t)last[0] + last[1];
+  TRY(scan_sum_total(c, flag, pos, n, c->stream, &nv, rd(kept, &hk)));
   if (d_start && nv) {
     iter_emit_kernel<<<grid_for(n), 256, 0, c->stream>>>(d_file, d_packed, flag, pos, n, nv, P<uint64_t>(c, B_IT_ST),
                                                          P<uint64_t>(c, B_IT_EN), d_start, d_end, d_meta, d_kh);
-    KCHK(c, "iter_emit_kernel");
-    HIPCHK(hipGetLastError());
+    LAUNCHED(c->stream, "iter_emit_kernel");
     HIPCHK(spin_sync(c->stream));
   }
   *n_out = nv;
@@ -647,21 +598,16 @@ extern "C" int srd_compact_device(srd_ctx* c, const uint8_t* d_file, uint64_t fl
   TRY(ensure(c, B_IT_PST, nv * 8));
   TRY(ensure(c, B_IT_ENT, nv * sizeof(srd_write_entry)));
   TRY(ensure(c, B_IT_KEPT, 64));
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)nv));
-  KCHK(c, "hipcub");
-  TRY(ensure(c, B_CUB_TMP, tb + 256));
+  TRY(ensure_scan(c, P<uint64_t>(c, B_IT_RLEN), P<uint64_t>(c, B_IT_PST), nv));
   compact_sizes_kernel<<<grid_for(nv), 256, 0, c->stream>>>(st, en, nv, P<uint64_t>(c, B_IT_RLEN));
-  KCHK(c, "compact_sizes_kernel");
+  LAUNCHED(c->stream, "compact_sizes_kernel");
   TRY(scan_sum(c, P<uint64_t>(c, B_IT_RLEN), P<uint64_t>(c, B_IT_PST), nv));
   uint64_t* d_new_len = P<uint64_t>(c, B_IT_KEPT) + 2;
   compact_entries_kernel<<<grid_for(nv), 256, 0, c->stream>>>(st, en, P<uint64_t>(c, B_IT_OKH), P<uint64_t>(c, B_IT_PST),
                                                              nv, P<srd_write_entry>(c, B_IT_ENT), d_new_len);
-  KCHK(c, "compact_entries_kernel");
-  HIPCHK(hipGetLastError());
+  LAUNCHED(c->stream, "compact_entries_kernel");
   uint64_t tail = 0;
-  HIPCHK(hipMemcpyAsync(&tail, d_new_len, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(spin_sync(c->stream));
+  TRY(read_small(c, c->stream, {rd(d_new_len, &tail)}));
   *new_len = tail;
   if (!d_out) return 0;
   if (tail > out_cap) { set_err("out_cap too small for the compacted store"); return SRD_ERR_ARG; }
@@ -673,8 +619,7 @@ extern "C" int srd_compact_device(srd_ctx* c, const uint8_t* d_file, uint64_t fl
                    d_key_hash_out ? d_key_hash_out : P<uint64_t>(c, B_WKH),
                    d_meta_off_out ? d_meta_off_out : P<uint64_t>(c, B_WMO), nullf));
   unsigned int hn = 0;
-  HIPCHK(hipMemcpyAsync(&hn, nullf, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(spin_sync(c->stream));
+  TRY(read_small(c, c->stream, {rd(nullf, &hn)}));
   if (hn) {  // write_stream rejects NULL-only payloads (data_store.rs:792-797); compact() fails with it
     set_err("NULL-byte-only streams cannot be written directly.");
     return SRD_ERR_ARG;
@@ -683,14 +628,8 @@ extern "C" int srd_compact_device(srd_ctx* c, const uint8_t* d_file, uint64_t fl
 }
 
 // ---------------------------------------------------------------------------
-// Verified payloads (srd_gather.hip): layout, one wait for the total, then the
+// Verified payloads (srd_gather.hip): layout, one wait for the totals, then the
 // unit table, the gather, the combine and the finish enqueued on the stream
-static int gather_scan(Ctx* c, const uint64_t* in, uint64_t* out, uint64_t n, hipStream_t s) {
-  size_t tb = c->bufs[B_CUB_TMP].n;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(P<void>(c, B_CUB_TMP), tb, in, out, (int)n, s));
-  return 0;
-}
-
 extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint64_t flen, const uint64_t* d_start,
                                          const uint64_t* d_end, uint64_t n, uint32_t flags, uint8_t* d_out,
                                          uint64_t out_cap, uint64_t* d_out_off, uint8_t* d_status,
@@ -711,7 +650,7 @@ extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint
     }
   }
   HIPCHK(hipSetDevice(c->device));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t s = stream_of(c, stream);
   if (!n) {
     HIPCHK(hipMemsetAsync(d_out_off, 0, 8, s));
     return 0;
@@ -723,9 +662,7 @@ extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint
   TRY(ensure(c, B_GA_CPRE, n * 8));
   TRY(ensure(c, B_GA_CRC, n * 4));
   TRY(ensure(c, B_GA_CNT, 64));
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n));
-  TRY(ensure(c, B_CUB_TMP, tb + 256));
+  TRY(ensure_scan(c, (const uint64_t*)nullptr, (uint64_t*)nullptr, n));  // both scans below
   PayloadGatherArgs a{};
   a.file = d_file;
   a.flen = flen;
@@ -746,18 +683,14 @@ extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint
   a.layout_only = !d_out && !verify;
   HIPCHK(hipMemsetAsync(a.cnt, 0, 8, s));
   payload_layout_kernel<<<grid_for(n), 256, 0, s>>>(a);
-  HIPCHK(hipGetLastError());
-  TRY(gather_scan(c, a.plen, a.off, n, s));
-  TRY(gather_scan(c, a.chk, a.cpre, n, s));
-  // the totals = the last query's exclusive sum + its own term (n items: n < 2^31 fits hipCUB's int count)
-  uint64_t* h = c->h_small + 24;
-  HIPCHK(hipMemcpyAsync(h, a.off + n - 1, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(h + 1, a.plen + n - 1, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(h + 2, a.cpre + n - 1, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(h + 3, a.chk + n - 1, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(h + 4, a.cnt, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(spin_sync(s));
-  const uint64_t tot = h[0] + h[1], units = h[2] + h[3], n_multi = h[4];
+  LAUNCHED(s, "payload_layout_kernel");
+  // both totals and the multi-chunk count on one wait (n < 2^31 fits hipCUB's int count)
+  uint64_t off_last = 0, plen_last = 0, units = 0;
+  unsigned long long n_multi = 0;
+  TRY(scan_sum(c, (const uint64_t*)a.plen, a.off, n, s));
+  TRY(scan_sum_total(c, (const uint64_t*)a.chk, a.cpre, n, s, &units, rd(a.off + n - 1, &off_last),
+                     rd(a.plen + n - 1, &plen_last), rd(a.cnt, &n_multi)));
+  const uint64_t tot = off_last + plen_last;
   *total = tot;
   a.total = tot;
   if (d_out && tot > out_cap) {
@@ -772,15 +705,14 @@ extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint
     a.raw = P<uint32_t>(c, B_GA_RAW);
     a.n_units = units;
     payload_units_kernel<<<grid_for(units), 256, 0, s>>>(a);
+    LAUNCHED(s, "payload_units_kernel");
     const unsigned g = (unsigned)std::min<uint64_t>((units + SCAN_WAVES_V2 - 1) / SCAN_WAVES_V2, c->scan_blocks);
     payload_gather_kernel<<<g, SCAN_WAVES_V2 * 64, 0, s>>>(a);
+    LAUNCHED(s, "payload_gather_kernel");
     if (n_multi) payload_combine_kernel<<<(unsigned)std::min<uint64_t>((n + 3) / 4, 4096), 256, 0, s>>>(a);
+    LAUNCHED(s, "payload_combine_kernel");
   }
   payload_finish_kernel<<<grid_for(n + 1), 256, 0, s>>>(a);
-  HIPCHK(hipGetLastError());
-  if (sync_debug()) {
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
-  }
+  LAUNCHED(s, "payload_finish_kernel");
   return 0;
 }

@@ -41,12 +41,12 @@ static int core_runs(Ctx* c, const int64_t* par, uint64_t n, const char* key_nam
   uint32_t* chead = P<uint32_t>(c, B_RUNHEAD);
   HIPCHK(hipMemsetAsync(core, 0, n, c->stream));
   child_kernel<<<nb, 256, 0, c->stream>>>(par, n, core);
-  KCHK(c, "child_kernel");
+  LAUNCHED(c->stream, "child_kernel");
   launch_key(nb, core, key);
-  KCHK(c, key_name);
+  LAUNCHED(c->stream, key_name);
   TRY(scan_max(c, key, chead, n));
   head_key_kernel<<<nb, 256, 0, c->stream>>>(core, par, chead, n, key);
-  KCHK(c, "head_key_kernel");
+  LAUNCHED(c->stream, "head_key_kernel");
   return scan_max(c, key, chead, n);
 }
 
@@ -60,25 +60,20 @@ static int walk_and_mark(Ctx* c, const int64_t* par, const uint64_t* slot, uint6
   }));
   walk_kernel<<<1, 64, 0, c->stream>>>(par, P<uint32_t>(c, B_RUNHEAD), slot, P<u32x4>(c, B_CREC),
                                        P<uint64_t>(c, B_INTS), ws, n);
-  KCHK(c, "walk_kernel");
-  HIPCHK(hipGetLastError());
-  static_assert(sizeof(WalkState) <= 64, "h_small[8..16)");
-  HIPCHK(hipMemcpyAsync(c->h_small + 8, ws, sizeof(WalkState), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(spin_sync(c->stream));
-  memcpy(hws, c->h_small + 8, sizeof(WalkState));
+  LAUNCHED(c->stream, "walk_kernel");
+  TRY(read_small(c, c->stream, {rd(ws, hws)}));
   if (hws->status != 1) return 0;
   mark_kernel<<<blocks(n, 256), 256, 0, c->stream>>>(P<uint64_t>(c, B_INTS), ws, n, core,
                                                      P<uint32_t>(c, B_ONPATH));
-  KCHK(c, "mark_kernel");
+  LAUNCHED(c->stream, "mark_kernel");
   HIPCHK(hipMemsetAsync(P<uint32_t>(c, B_ONPATH) + n, 0, 4, c->stream));
   TRY(scan_sum(c, P<uint32_t>(c, B_ONPATH), P<uint32_t>(c, B_CPOS), n + 1));
   scatter_chain_kernel<<<blocks(n, 256), 256, 0, c->stream>>>(P<uint32_t>(c, B_ONPATH), P<uint32_t>(c, B_CPOS), n,
                                                               map, P<uint64_t>(c, B_CHAIN_G));
-  KCHK(c, "scatter_chain_kernel");
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(c->h_small + 8, P<uint32_t>(c, B_CPOS) + n, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(spin_sync(c->stream));
-  hws->chain_len = 1 + (uint64_t)(uint32_t)c->h_small[8];
+  LAUNCHED(c->stream, "scatter_chain_kernel");
+  uint32_t on_path = 0;
+  TRY(read_small(c, c->stream, {rd(P<uint32_t>(c, B_CPOS) + n, &on_path)}));
+  hws->chain_len = 1 + (uint64_t)on_path;
   return 0;
 }
 
@@ -176,12 +171,10 @@ static int finish(Ctx* c, const uint8_t* d_file, uint64_t flen, uint64_t n, uint
   f.n_bad = (unsigned long long*)(cnt + 6);
   if (n) {
     finalize_kernel<<<blocks(n, 256), 256, 0, c->stream>>>(f);
-    KCHK(c, "finalize_kernel");
-    HIPCHK(hipGetLastError());
+    LAUNCHED(c->stream, "finalize_kernel");
     if (!f.no_crc) {
       slow_kernel<<<2048 / SLOW_WAVES, SLOW_WAVES * 64, 0, c->stream>>>(f);
-      KCHK(c, "slow_kernel");
-      HIPCHK(hipGetLastError());
+      LAUNCHED(c->stream, "slow_kernel");
     }
   }
   // ---- KeyIndexer::build (bucketed; the global table if a bucket overflows) ----
@@ -192,7 +185,7 @@ static int finish(Ctx* c, const uint8_t* d_file, uint64_t flen, uint64_t n, uint
                       P<uint64_t>(c, B_IPACKED), &nidx));
   if (!n) HIPCHK(spin_sync(c->stream));  // index_build_sep waited only for n > 0
   uint64_t h[8];
-  memcpy(h, c->h_small, 64);
+  counters_landed(c, h);
   out->n_index = nidx;
   out->n_crc_bad = h[6];
   out->n_chain = n;
@@ -226,13 +219,10 @@ static int run_scan(Ctx* c, const uint8_t* d_file, uint64_t flen, uint64_t* K, u
       hipEvent_t e0, e1;
       TRY(next_scan_events(c, &e0, &e1));
       launch_scan<true>(g, a, c->stream, e0, e1);
-      KCHK(c, "scan_kernel");
-      HIPCHK(hipGetLastError());
+      LAUNCHED(c->stream, "scan_kernel");
     }
     TRY(scan_sum(c, P<uint32_t>(c, B_SPAN_COUNT), P<uint64_t>(c, B_SPAN_BASE), n_spans + 1));
-    TRY(enqueue_small(c, P<uint64_t>(c, B_SPAN_BASE) + n_spans, 0));
-    TRY(read_counters(c, h));
-    *K = c->h_small[8];
+    TRY(read_counters(c, h, P<uint64_t>(c, B_SPAN_BASE) + n_spans, K));
     if (*K >= 0xFFFFFFFFull) { set_err("more than 2^32 - 2 chain-node candidates (full pass)"); return SRD_ERR_ALLOC; }
     if ((uint32_t)h[2] == 0) break;
     if (c->cfull.cap >= SPAN_BYTES) { set_err("candidate overflow"); return SRD_ERR_INTERNAL; }
@@ -253,8 +243,7 @@ static int run_scan(Ctx* c, const uint8_t* d_file, uint64_t flen, uint64_t* K, u
     l.d_par = P<int64_t>(c, B_DPAR);
     l.d_slot = P<uint64_t>(c, B_DSLOT);
     link_kernel<<<blocks(n_spans, 256 / LINK_LANES), 256, 0, c->stream>>>(l);
-    KCHK(c, "link_kernel");
-    HIPCHK(hipGetLastError());
+    LAUNCHED(c->stream, "link_kernel");
   } else {
     TRY(alloc_dense(c, 1));
   }
@@ -336,8 +325,7 @@ static int opt_scan(Ctx* c, OptAttempt& o, const ScanPart& part, unsigned g, uin
   hipEvent_t e0, e1;
   TRY(next_scan_events(c, &e0, &e1));
   launch_scan<false>(g, a, c->stream, e0, e1);
-  KCHK(c, "scan_kernel");
-  HIPCHK(hipGetLastError());
+  LAUNCHED(c->stream, "scan_kernel");
   return 0;
 }
 
@@ -416,27 +404,26 @@ static int opt_glue(Ctx* c, const OptAttempt& o, Plan* hp) {
       if (rounds == 2) {  // the retry's first marks: the nodes the link claims were made on
         sa.gen = mgen;
         marks_from_claims_kernel<<<GLUE_BLOCKS, GLUE_THREADS, 0, c->stream>>>(sa, marks);
-        KCHK(c, "marks_from_claims_kernel");
+        LAUNCHED(c->stream, "marks_from_claims_kernel");
       }
       for (int r = 0; r < 2; r++) {  // two more prune rounds per retry
         sa.has_child = marks;
         sa.gen = mgen;
         const uint32_t g2 = ++c->gen;
         prune_kernel<<<GLUE_BLOCKS, GLUE_THREADS, 0, c->stream>>>(sa, marks2, g2);
-        KCHK(c, "prune_kernel");
+        LAUNCHED(c->stream, "prune_kernel");
         std::swap(marks, marks2);
         mgen = g2;
       }
       sa.has_child = marks;
       sa.gen = mgen;
       child2_kernel<<<GLUE_BLOCKS, GLUE_THREADS, 0, c->stream>>>(sa);  // core-only claims
-      KCHK(c, "child2_kernel");
+      LAUNCHED(c->stream, "child2_kernel");
     }
     const bool fused = rounds == 0 && c->glue_fused;
     if (!fused) {
       check_kernel<<<CHAIN_BLOCKS, CHAIN_THREADS, 0, c->stream>>>(sa);
-      KCHK(c, "check_kernel");
-      HIPCHK(hipGetLastError());
+      LAUNCHED(c->stream, "check_kernel");
     }
     // ---- plan + chain ranks + per-entry outputs / CRC + index histogram ----
     FinArgs f = fin_args(c, o.d_file, o.flen, o.flags);
@@ -452,8 +439,7 @@ static int opt_glue(Ctx* c, const OptAttempt& o, Plan* hp) {
     else
       chain_finalize_kernel<false><<<CHAIN_BLOCKS, CHAIN_THREADS, (1u << log2_nbk) * 4, c->stream>>>(
           sa, f, index_args(c, log2_nbk), log2_nbk, lb);
-    KCHK(c, "chain_finalize_kernel");
-    HIPCHK(hipGetLastError());
+    LAUNCHED(c->stream, "chain_finalize_kernel");
     // ---- KeyIndexer::build, bucketed ----
     TRY(launch_index_bucketed(c, f.o_kh, f.o_mo, &pl->n_chain, &pl->status, log2_nbk, P<uint64_t>(c, B_IKEY),
                               P<uint64_t>(c, B_IPACKED), pl, true, &f, false, o.xp ? &o.xp->scan_ticks : nullptr));
@@ -552,7 +538,7 @@ static int optimistic_pass(Ctx* c, const uint8_t* d_span, uint64_t span_off, uin
     // every record's node test, parent and claim (slot space), one block per scan wave
     link2_kernel<<<(unsigned)((o.total_waves + LINK_WPB - 1) / LINK_WPB), 256 * LINK_WPB, 0, c->stream>>>(
         o.a, (uint32_t)o.total_waves);
-    KCHK(c, "link2_kernel");
+    LAUNCHED(c->stream, "link2_kernel");
     if (o.xp) {  // link2 wrote the next call's block starts into the other half
       c->xp_par ^= 1u;
       c->xp_valid = true;
@@ -624,7 +610,7 @@ static int full_pass(Ctx* c, const uint8_t* d_file, uint64_t flen, uint32_t flag
       core_flag_key_kernel<<<nb, 256, 0, c->stream>>>(co, K, key);
     }));
     status_init_kernel<<<kb, 256, 0, c->stream>>>(par, core, chead, K, st, jmp);
-    KCHK(c, "status_init_kernel");
+    LAUNCHED(c->stream, "status_init_kernel");
     uint64_t* cnt = P<uint64_t>(c, B_COUNTERS);
     // pointer jumping over the core run heads: every round doubles how far
     // each unresolved head looks along its chain of runs, so ceil(log2 K) + 1
@@ -645,29 +631,27 @@ static int full_pass(Ctx* c, const uint8_t* d_file, uint64_t flen, uint32_t flag
         // a fixed grid (grid-stride): a round after convergence exits at once
         status_round_kernel<<<std::min(kb, 1024u), 256, 0, c->stream>>>(K, core, chead, st, jmp, rflag + r,
                                                                        r ? rflag + r - 1 : nullptr);
-        KCHK(c, "status_round_kernel");
+        LAUNCHED(c->stream, "status_round_kernel");
       }
       HIPCHK(hipMemsetAsync(cnt + 4, 0, 8, c->stream));
       status_round_kernel<<<std::min(kb, 1024u), 256, 0, c->stream>>>(K, core, chead, st, jmp, (unsigned int*)(cnt + 4),
                                                                      nullptr);
-      KCHK(c, "status_round_kernel");
-      HIPCHK(hipGetLastError());
+      LAUNCHED(c->stream, "status_round_kernel");
       TRY(read_counters(c, h));
       if (!h[4]) break;
       if (pass == 7) { set_err("internal: pointer jumping did not converge"); return SRD_ERR_INTERNAL; }
     }
     status_spread_core_kernel<<<kb, 256, 0, c->stream>>>(K, core, chead, st);
-    KCHK(c, "status_spread_core_kernel");
+    LAUNCHED(c->stream, "status_spread_core_kernel");
     status_spread_leaf_kernel<<<kb, 256, 0, c->stream>>>(K, par, core, st);
-    KCHK(c, "status_spread_leaf_kernel");
+    LAUNCHED(c->stream, "status_spread_leaf_kernel");
     const unsigned vb = blocks(K, 256);
     TRY(ensure(c, B_JMP, std::max<uint64_t>(K, vb) * 8));  // per-block maxima (the jump pointers are dead now)
     valid_max_kernel<<<vb, 256, 0, c->stream>>>(P<uint8_t>(c, B_ST), K, P<uint64_t>(c, B_JMP), P<uint32_t>(c, B_VFLAG));
-    KCHK(c, "valid_max_kernel");
+    LAUNCHED(c->stream, "valid_max_kernel");
     max_reduce_kernel<<<1, 1024, 0, c->stream>>>(P<uint64_t>(c, B_JMP), vb, (unsigned long long*)(cnt + 3),
                                                  P<uint64_t>(c, B_DM), (unsigned long long*)(cnt + 7));
-    KCHK(c, "max_reduce_kernel");
-    HIPCHK(hipGetLastError());
+    LAUNCHED(c->stream, "max_reduce_kernel");
     TRY(read_counters(c, h));
     best_g1 = h[3];
     if (best_g1) tlin = h[7] + 20;  // d_m[best_g1 - 1] + 20
@@ -693,19 +677,17 @@ static int full_pass(Ctx* c, const uint8_t* d_file, uint64_t flen, uint32_t flag
   compact_valid_kernel<<<blocks(K, 256), 256, 0, c->stream>>>(P<uint32_t>(c, B_VFLAG), P<uint32_t>(c, B_VSCAN), K,
                                                               P<uint64_t>(c, B_VLIST), P<uint64_t>(c, B_VPOS),
                                                               P<uint64_t>(c, B_NV));
-  KCHK(c, "compact_valid_kernel");
+  LAUNCHED(c->stream, "compact_valid_kernel");
   remap_kernel<<<blocks(K, 256), 256, 0, c->stream>>>(P<uint64_t>(c, B_VLIST), P<uint64_t>(c, B_NV),
                                                       P<int64_t>(c, B_DPAR), P<uint64_t>(c, B_VPOS),
                                                       P<int64_t>(c, B_VPAR), P<uint64_t>(c, B_VSLOT),
                                                       P<uint64_t>(c, B_DSLOT));
-  KCHK(c, "remap_kernel");
+  LAUNCHED(c->stream, "remap_kernel");
   // the walk starts at the best node's compacted position
   walk_start_kernel<<<1, 64, 0, c->stream>>>(P<WalkState>(c, B_WALK), P<uint64_t>(c, B_VPOS), best_g1 - 1);
-  KCHK(c, "walk_start_kernel");
-  HIPCHK(hipGetLastError());
-  TRY(enqueue_small(c, P<uint64_t>(c, B_NV), 0));
-  HIPCHK(spin_sync(c->stream));
-  const uint64_t nv = c->h_small[8];
+  LAUNCHED(c->stream, "walk_start_kernel");
+  uint64_t nv = 0;
+  TRY(read_small(c, c->stream, {rd(P<uint64_t>(c, B_NV), &nv)}));
   WalkState hw{};
   TRY(walk_and_mark(c, P<int64_t>(c, B_VPAR), P<uint64_t>(c, B_VSLOT), nv, P<uint64_t>(c, B_VLIST), &hw));
   if (hw.status != 1) { set_err("internal: valid walk did not reach a root"); return SRD_ERR_INTERNAL; }

@@ -834,15 +834,33 @@ def batch_write(keys, payloads, tail: int = 0, allow_null: bool = False, ctx: Co
     base = tail & ~63
     cap = max(int(nt.value) - base, 1)
     dev = torch.zeros(cap + 64, dtype=torch.uint8, device=f"cuda:{_ctx_device(ctx)}")
+    _after_torch(ctx, dev.device)
     new_tail, kh, mo = batch_write_raw(dev.data_ptr(), cap, tail, kb.ctypes.data, ko, kl, pb.ctypes.data, po, pl,
                                        flags, ctx)
-    torch.cuda.synchronize()
+    _sync_ctx(ctx, dev.device)
     out = dev[tail - base: new_tail - base].cpu().numpy().tobytes()
     return new_tail, out, [int(x) for x in kh], [int(x) for x in mo]
 
 
 def _ctx_device(ctx: Context) -> int:
     return int(os.environ.get("SRD_DEVICE", "0")) if ctx is None else getattr(ctx, "device", 0)
+
+
+def _after_torch(ctx: Context, device):  # (DESIGN.md section 10's stream rule: this and _sync_ctx)
+    """The context stream waits for torch's current stream (inputs torch wrote): an event, no host wait."""
+    import torch
+    torch.cuda.ExternalStream(ctx.stream, device=device).wait_stream(torch.cuda.current_stream(device))
+
+
+def _sync_ctx(ctx: Context, device):
+    """The host waits for the context stream (before torch reads what the library wrote)."""
+    import torch
+    torch.cuda.ExternalStream(ctx.stream, device=device).synchronize()
+
+
+def _same_len(a, b, what: str):
+    if len(a) != len(b):
+        raise ValueError(f"Mismatched lengths for {what}.")
 
 
 # ---------------------------------------------------------------------------
@@ -917,8 +935,7 @@ def gather_ranges(d_file: int, file_len: int, st, en, flags: int = 0, ctx: "Cont
     offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
     status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
     crc = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    lib_stream = torch.cuda.ExternalStream(ctx.stream, device=dev)
-    lib_stream.wait_stream(torch.cuda.current_stream(dev))
+    _after_torch(ctx, dev)
     args = (d_file, file_len, st.data_ptr(), en.data_ptr(), n)
     data = None
     if flags & GATHER_VERIFY_ONLY:
@@ -926,11 +943,11 @@ def gather_ranges(d_file: int, file_len: int, st, en, flags: int = 0, ctx: "Cont
     else:
         total = payload_gather_device(*args, flags, None, 0, offs.data_ptr(), status.data_ptr(), None, ctx)
         data = torch.empty(total, dtype=torch.uint8, device=dev)
-        lib_stream.wait_stream(torch.cuda.current_stream(dev))
+        _after_torch(ctx, dev)
         # (no hit at all: nothing to copy, the verify-only call completes statuses and CRCs)
         payload_gather_device(*args, flags if total else flags | GATHER_VERIFY_ONLY, data.data_ptr() if total else None,
                               total, offs.data_ptr(), status.data_ptr(), crc.data_ptr(), ctx)
-    lib_stream.synchronize()
+    _sync_ctx(ctx, dev)
     o = offs.cpu().numpy().view(np.uint64)
     s = status[:n].cpu().numpy()
     ln = (en - st).cpu().numpy().view(np.uint64).copy()
@@ -957,16 +974,10 @@ class DeviceIndex:
     # -- kept live: reindex (data_store.rs:224-259) on the table in place -----------------
 
     def _lib_after_torch(self):
-        """The context stream waits for what torch's current stream holds (inputs
-        torch wrote): an event, no host wait."""
-        import torch
-        dev = self.table.device
-        torch.cuda.ExternalStream(self.ctx.stream, device=dev).wait_stream(torch.cuda.current_stream(dev))
+        _after_torch(self.ctx, self.table.device)
 
     def _sync_lib(self):
-        """The host waits for the context stream (before torch reads what the library wrote)."""
-        import torch
-        torch.cuda.ExternalStream(self.ctx.stream, device=self.table.device).synchronize()
+        _sync_ctx(self.ctx, self.table.device)
 
     def _as_dev(self, a, dtype=np.uint64):
         import torch
@@ -1059,41 +1070,17 @@ class DeviceIndex:
         ones = torch.ones(kh.numel(), dtype=torch.uint8, device=self.table.device)
         return self.apply(kh, torch.zeros_like(kh), ones)[2]
 
-    def _dev_u64(self, a):
-        import torch
-        return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64)).to(self.table.device)
-
     def get_packed(self, hashes) -> np.ndarray:
         """KeyIndexer::get_packed for each hash (INDEX_NONE when absent)."""
         import torch
-        q = self._dev_u64(hashes)
+        q = self._as_dev(hashes)
         out = torch.empty_like(q)
-        n = q.numel()
+        self._lib_after_torch()
         _check(lib().srd_index_get_packed_device(self.ctx.h, C.c_void_p(self.table.data_ptr()), self.nbytes,
-                                                 C.c_void_p(q.data_ptr()), n, C.c_void_p(out.data_ptr()),
+                                                 C.c_void_p(q.data_ptr()), q.numel(), C.c_void_p(out.data_ptr()),
                                                  C.c_void_p(self.ctx.stream)))
-        torch.cuda.synchronize()
+        self._sync_lib()
         return out.cpu().numpy().view(np.uint64)
-
-    def batch_read_hashed_keys(self, d_file: int, file_len: int, hashes, non_hashed_keys=None):
-        """batch_read_hashed_keys: [(start, end) | None] in query order; with
-        non_hashed_keys, each read is verified by tag_from_key (data_store.rs:513-521)."""
-        import torch
-        if non_hashed_keys is not None and len(non_hashed_keys) != len(hashes):
-            raise ValueError("Mismatched lengths for hashed and non-hashed keys.")
-        q = self._dev_u64(hashes)
-        v = self._dev_u64(compute_hash_batch(non_hashed_keys, self.ctx)) if non_hashed_keys is not None else None
-        n = q.numel()
-        st, en = torch.empty_like(q), torch.empty_like(q)
-        torch.cuda.synchronize()
-        _check(lib().srd_batch_read_hashed_device(self.ctx.h, C.c_void_p(self.table.data_ptr()), self.nbytes,
-                                                  C.c_void_p(d_file), file_len, C.c_void_p(q.data_ptr()),
-                                                  C.c_void_p(v.data_ptr()) if v is not None else None, n,
-                                                  C.c_void_p(st.data_ptr()), C.c_void_p(en.data_ptr()),
-                                                  C.c_void_p(self.ctx.stream)))
-        torch.cuda.synchronize()
-        s, e = st.cpu().numpy().view(np.uint64), en.cpu().numpy().view(np.uint64)
-        return [None if a == b else (int(a), int(b)) for a, b in zip(s, e)]
 
     def _ranges_device(self, d_file: int, file_len: int, hashes, verify=None):
         """srd_batch_read_hashed_device on the context stream: the ranges stay on
@@ -1110,17 +1097,33 @@ class DeviceIndex:
                                                   C.c_void_p(self.ctx.stream)))
         return st, en, (q, v)  # (the inputs live until the caller has waited)
 
+    def _ranges_host(self, d_file: int, file_len: int, hashes, verify=None):
+        """... waited for and copied to the host: two uint64 arrays (start == end: None)."""
+        st, en, _keep = self._ranges_device(d_file, file_len, hashes, verify)
+        self._sync_lib()
+        return st.cpu().numpy().view(np.uint64), en.cpu().numpy().view(np.uint64)
+
+    def batch_read_hashed_keys(self, d_file: int, file_len: int, hashes, non_hashed_keys=None):
+        """batch_read_hashed_keys: [(start, end) | None] in query order; with
+        non_hashed_keys, each read is verified by tag_from_key (data_store.rs:513-521)."""
+        if non_hashed_keys is not None:
+            _same_len(non_hashed_keys, hashes, "hashed and non-hashed keys")
+        v = compute_hash_batch(non_hashed_keys, self.ctx) if non_hashed_keys is not None else None
+        s, e = self._ranges_host(d_file, file_len, hashes, v)
+        return [None if a == b else (int(a), int(b)) for a, b in zip(s, e)]
+
     def batch_gather(self, d_file: int, file_len: int, hashes, non_hashed_keys=None, flags: int = 0) -> GatherResult:
         """batch_read_hashed_keys with the payloads: the look-up and the verified
         gather (srd_payload_gather_device) on the device, one GatherResult in query
         order -- a read's bytes plus EntryHandle::is_valid_checksum for each."""
-        if non_hashed_keys is not None and len(non_hashed_keys) != len(hashes):
-            raise ValueError("Mismatched lengths for hashed and non-hashed keys.")
+        if non_hashed_keys is not None:
+            _same_len(non_hashed_keys, hashes, "hashed and non-hashed keys")
         v = compute_hash_batch(non_hashed_keys, self.ctx) if non_hashed_keys is not None else None
-        st, en, keep = self._ranges_device(d_file, file_len, hashes, v)
-        r = gather_ranges(d_file, file_len, st, en, flags, self.ctx)
-        del keep
-        return r
+        return self._gather(d_file, file_len, hashes, v, flags)
+
+    def _gather(self, d_file: int, file_len: int, hashes, verify, flags: int) -> GatherResult:
+        st, en, _keep = self._ranges_device(d_file, file_len, hashes, verify)  # (alive until the gather has waited)
+        return gather_ranges(d_file, file_len, st, en, flags, self.ctx)
 
     def batch_read(self, d_file: int, file_len: int, keys):
         """batch_read (data_store.rs:1111-1115): host keys, hashed and verified on the device."""
@@ -1137,18 +1140,23 @@ class DeviceIndex:
 # EntryIterator / par_iter_entries, estimate_compaction_savings and compact
 # over the device index (data_store.rs:297-361, 605-749; entry_iterator.rs:69-126)
 
+def _iter_entries(d_file: int, file_len: int, d_index_packed: int, n_index: int, ctx: Context):
+    """srd_iter_entries_device (synchronises): device int64 tensors (start, end, meta_off, key_hash)."""
+    import torch
+    dev = torch.device(f"cuda:{ctx.device}")
+    outs = [torch.empty(max(n_index, 1), dtype=torch.int64, device=dev) for _ in range(4)]
+    n = C.c_uint64()
+    _after_torch(ctx, dev)
+    _check(lib().srd_iter_entries_device(ctx.h, C.c_void_p(d_file), file_len, C.c_void_p(d_index_packed), n_index,
+                                         *[C.c_void_p(t.data_ptr()) for t in outs], C.byref(n)))
+    return tuple(t[: int(n.value)] for t in outs)
+
+
 def iter_entries_device(d_file: int, file_len: int, d_index_packed: int, n_index: int, ctx: Context | None = None):
     """The latest non-tombstone entry per key, newest first (EntryIterator
     order): numpy arrays (start, end, meta_off, key_hash)."""
-    import torch
-    ctx = ctx or default_ctx()
-    dev = f"cuda:{ctx.device}"
-    outs = [torch.empty(max(n_index, 1), dtype=torch.int64, device=dev) for _ in range(4)]
-    n = C.c_uint64()
-    _check(lib().srd_iter_entries_device(ctx.h, C.c_void_p(d_file), file_len, C.c_void_p(d_index_packed), n_index,
-                                         *[C.c_void_p(t.data_ptr()) for t in outs], C.byref(n)))
-    k = int(n.value)
-    return tuple(t[:k].cpu().numpy().view(np.uint64) for t in outs)
+    outs = _iter_entries(d_file, file_len, d_index_packed, n_index, ctx or default_ctx())
+    return tuple(t.cpu().numpy().view(np.uint64) for t in outs)
 
 
 def estimate_compaction_savings_device(d_file: int, file_len: int, d_index_packed: int, n_index: int,
@@ -1164,13 +1172,16 @@ def compact_device(d_file: int, file_len: int, d_index_packed: int, n_index: int
     """compact(): the compacted store's bytes as a device tensor."""
     import torch
     ctx = ctx or default_ctx()
+    dev = torch.device(f"cuda:{ctx.device}")
     nl = C.c_uint64()
+    _after_torch(ctx, dev)
     _check(lib().srd_compact_device(ctx.h, C.c_void_p(d_file), file_len, C.c_void_p(d_index_packed), n_index, None,
                                     0, C.byref(nl), None, None))
-    out = torch.zeros(max(int(nl.value), 1) + 64, dtype=torch.uint8, device=f"cuda:{ctx.device}")
+    out = torch.zeros(max(int(nl.value), 1) + 64, dtype=torch.uint8, device=dev)
+    _after_torch(ctx, dev)
     _check(lib().srd_compact_device(ctx.h, C.c_void_p(d_file), file_len, C.c_void_p(d_index_packed), n_index,
                                     C.c_void_p(out.data_ptr()), out.numel(), C.byref(nl), None, None))
-    torch.cuda.synchronize()
+    _sync_ctx(ctx, dev)
     return out[: int(nl.value)]
 
 
@@ -1207,8 +1218,7 @@ class DeviceStore:
         ctx = ctx or default_ctx()
         if dev_tensor.numel() < padded_size(file_len):
             raise ValueError("the store buffer must hold padded_size(file_len) bytes")
-        torch.cuda.ExternalStream(ctx.stream, device=dev_tensor.device).wait_stream(
-            torch.cuda.current_stream(dev_tensor.device))
+        _after_torch(ctx, dev_tensor.device)
         r = validate_index_device(dev_tensor.data_ptr(), file_len, 0, ctx)  # synchronises
         return cls(dev_tensor, int(r.final_len), DeviceIndex(r.index_key_hash, r.index_packed, int(r.n_index), ctx), ctx)
 
@@ -1232,8 +1242,7 @@ class DeviceStore:
     def batch_write(self, keys, payloads) -> int:
         """DataStoreWriter::batch_write (data_store.rs:838-843): compute_hash_batch,
         then batch_write_with_key_hashes."""
-        if len(keys) != len(payloads):
-            raise ValueError("Mismatched lengths for keys and payloads.")
+        _same_len(keys, payloads, "keys and payloads")
         return self.batch_write_with_key_hashes(compute_hash_batch(keys, self.ctx), payloads, False)
 
     def batch_write_with_key_hashes(self, hashes, payloads, allow_null: bool = False) -> int:
@@ -1244,8 +1253,7 @@ class DeviceStore:
         capacity raises ValueError before anything is written."""
         import torch
         n = len(payloads)
-        if len(hashes) != n:
-            raise ValueError("Mismatched lengths for key hashes and payloads.")
+        _same_len(hashes, payloads, "key hashes and payloads")
         if not n:
             return self._tail
         payloads = [bytes(p) for p in payloads]
@@ -1313,19 +1321,7 @@ class DeviceStore:
     # -- reads ----------------------------------------------------------------------------
 
     def _ranges(self, hashes, verify):
-        import torch
-        idx = self.index
-        q = idx._as_dev(hashes)
-        v = idx._as_dev(verify) if verify is not None else None
-        st, en = torch.empty_like(q), torch.empty_like(q)
-        idx._lib_after_torch()
-        _check(lib().srd_batch_read_hashed_device(self.ctx.h, C.c_void_p(idx.table.data_ptr()), idx.nbytes,
-                                                  C.c_void_p(self.buf.data_ptr()), self._tail, C.c_void_p(q.data_ptr()),
-                                                  C.c_void_p(v.data_ptr()) if v is not None else None, q.numel(),
-                                                  C.c_void_p(st.data_ptr()), C.c_void_p(en.data_ptr()),
-                                                  C.c_void_p(self.ctx.stream)))
-        idx._sync_lib()
-        return st.cpu().numpy().view(np.uint64), en.cpu().numpy().view(np.uint64)
+        return self.index._ranges_host(self.buf.data_ptr(), self._tail, hashes, verify)
 
     def _payloads(self, st, en):
         import torch
@@ -1353,8 +1349,8 @@ class DeviceStore:
     def batch_read_hashed_keys(self, hashes, non_hashed_keys=None):
         """data_store.rs:1111-1158: with non_hashed_keys each read is verified by
         tag_from_key (:513-521)."""
-        if non_hashed_keys is not None and len(non_hashed_keys) != len(hashes):
-            raise ValueError("Mismatched lengths for hashed and non-hashed keys.")
+        if non_hashed_keys is not None:
+            _same_len(non_hashed_keys, hashes, "hashed and non-hashed keys")
         if not len(hashes):
             return []
         v = compute_hash_batch(non_hashed_keys, self.ctx) if non_hashed_keys is not None else None
@@ -1374,13 +1370,7 @@ class DeviceStore:
         payloads of `keys` gathered into one device buffer, each checked against
         its stored checksum (every read verified by its key's own tag)."""
         h = compute_hash_batch(keys, self.ctx) if len(keys) else []
-        return self._gather_hashed(h, h, flags)
-
-    def _gather_hashed(self, hashes, verify, flags):
-        st, en, keep = self.index._ranges_device(self.buf.data_ptr(), self._tail, hashes, verify)
-        r = gather_ranges(self.buf.data_ptr(), self._tail, st, en, flags, self.ctx)
-        del keep
-        return r
+        return self.index._gather(self.buf.data_ptr(), self._tail, h, h, flags)
 
     def batch_gather_hashed_keys(self, hashes, non_hashed_keys=None, flags: int = 0) -> GatherResult:
         """batch_read_hashed_keys (data_store.rs:1111-1158) with the payloads verified."""
@@ -1395,14 +1385,6 @@ class DeviceStore:
         """Every live payload in EntryIterator order (newest first), gathered and
         verified: the index's export, srd_iter_entries_device, then the gather of
         its ranges."""
-        import torch
         _k, p = self.index.export()  # synchronises
-        n = p.numel()
-        outs = [torch.empty(max(n, 1), dtype=torch.int64, device=self.buf.device) for _ in range(4)]
-        got = C.c_uint64()
-        self.index._lib_after_torch()
-        _check(lib().srd_iter_entries_device(self.ctx.h, C.c_void_p(self.buf.data_ptr()), self._tail,
-                                             C.c_void_p(p.data_ptr()), n, *[C.c_void_p(t.data_ptr()) for t in outs],
-                                             C.byref(got)))  # synchronises
-        k = int(got.value)
-        return gather_ranges(self.buf.data_ptr(), self._tail, outs[0][:k], outs[1][:k], 0, self.ctx)
+        st, en, _mo, _kh = _iter_entries(self.buf.data_ptr(), self._tail, p.data_ptr(), p.numel(), self.ctx)
+        return gather_ranges(self.buf.data_ptr(), self._tail, st, en, 0, self.ctx)

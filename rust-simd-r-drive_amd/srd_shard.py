@@ -97,7 +97,7 @@ class HipBackend:
     def _after_torch(self, t: torch.Tensor):
         # inputs written on torch's stream (copies, the RCCL collectives):
         # the library's own stream waits for them (an event, no host sync)
-        torch.cuda.ExternalStream(self.ctx.stream, device=t.device).wait_stream(torch.cuda.current_stream(t.device))
+        S._after_torch(self.ctx, t.device)
 
     def validate_span(self, buf: torch.Tensor, span_off: int, lo: int, hi: int, flags: int = 0):
         self._after_torch(buf)

@@ -1,0 +1,222 @@
+// ASan/UBSan check of the device index table's rule (TEST INFRASTRUCTURE):
+// rust-simd-r-drive_amd/csrc/srd_table.h compiled for the host -- the probe,
+// the claim and the slot states the table's kernels run, with the claim's CAS
+// as a plain compare-and-store -- single-threaded against a std::unordered_map:
+//   - a probe chain of 12 keys that share home slot 60 of a 64-slot table and
+//     so wraps from slot 63 to slot 0: all inserted in probe order, all found;
+//   - one in the middle deleted: the later ones are still found, the deleted
+//     one reads as absent, an absent key's probe runs past it to the first
+//     empty slot; re-inserted it takes its own slot and no new one;
+//   - key hashes 0 and 2^64 - 1 are ordinary keys;
+//   - seeded runs of 10 000 inserts, updates, deletes and finds at capacities
+//     64 and 1024 stay equal to the model, never hold more than capacity / 2
+//     non-empty slots, and at exactly capacity / 2 a new key is refused
+//     (table_admits, the rule the apply admits a batch by);
+//   - the size arithmetic: capacity, table_log2cap, table_ok, table_view.
+// Exit status 0 = no sanitizer report and every check held.
+#include <stdint.h>
+#include <stdio.h>
+
+#include <unordered_map>
+#include <unordered_set>
+#include <vector>
+
+#include "srd_table.h"
+
+using namespace srd;
+
+static int g_fail = 0;
+#define EXPECT(c)                                                                  \
+  do {                                                                             \
+    if (!(c)) {                                                                    \
+      if (g_fail < 20) fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #c); \
+      g_fail++;                                                                    \
+    }                                                                              \
+  } while (0)
+
+static uint64_t rng_state = 0x5EEDull;
+static uint64_t rnd() {  // splitmix64
+  uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// A table in host memory, maintained the way the apply maintains the device's:
+// a key with a slot (live or deleted) is stored into it, a new key is admitted
+// by table_admits and claims a slot.
+struct HostTable {
+  std::vector<uint64_t> mem;
+  Table t;
+  uint64_t used = 0;  // slots that are not empty
+  explicit HostTable(uint64_t n_keys) : mem(table_bytes_for(n_keys) / 8) {
+    EXPECT(table_ok(mem.data(), mem.size() * 8));
+    t = table_view(mem.data(), mem.size() * 8);
+    for (uint64_t s = 0; s < cap(); s++) t.packed[s] = TBL_EMPTY;
+  }
+  uint64_t cap() const { return 1ull << t.log2cap; }
+  bool put(uint64_t k, uint64_t v, uint64_t* slot = nullptr) {
+    uint64_t s;
+    if (table_find(t, k, &s) != TBL_EMPTY) {
+      t.packed[s] = v;  // update, or revival of the key's own deleted slot
+    } else {
+      if (!table_admits(used, 1, t.log2cap)) return false;
+      s = table_claim(t, k, v);
+      used++;
+    }
+    if (slot) *slot = s;
+    return true;
+  }
+  void del(uint64_t k) {
+    uint64_t s;
+    const uint64_t p = table_find(t, k, &s);
+    if (p != TBL_EMPTY && p != TBL_DELETED) t.packed[s] = TBL_DELETED;
+  }
+  uint64_t non_empty() const {
+    uint64_t c = 0;
+    for (uint64_t s = 0; s < cap(); s++) c += t.packed[s] != TBL_EMPTY;
+    return c;
+  }
+};
+
+static uint64_t value_of(uint64_t k, uint64_t off) { return (k >> 48 << 48) | (off & 0xFFFFFFFFFFull); }
+
+static void chain_check() {
+  // keys whose home slot at capacity 64 is 60, by brute force
+  std::vector<uint64_t> ks;
+  for (uint64_t k = 1; ks.size() < 13; k++)
+    if (idx_slot(k * 0xD6E8FEB86659FD93ull, 6) == 60) ks.push_back(k * 0xD6E8FEB86659FD93ull);
+  const uint64_t absent = ks.back();
+  ks.pop_back();
+  HostTable h(32);
+  EXPECT(h.cap() == 64);
+  for (size_t i = 0; i < ks.size(); i++) {
+    uint64_t s = ~0ull;
+    EXPECT(h.put(ks[i], value_of(ks[i], i), &s));
+    EXPECT(s == ((60 + i) & 63));  // 60 .. 63, then 0 .. 7
+  }
+  for (size_t i = 0; i < ks.size(); i++) EXPECT(table_get(h.t, ks[i]) == value_of(ks[i], i));
+  uint64_t s = ~0ull;
+  EXPECT(table_find(h.t, absent, &s) == TBL_EMPTY && s == 8);
+  // delete one in the middle of the chain (slot 1, behind the wrap)
+  const size_t mid = 5;
+  h.del(ks[mid]);
+  EXPECT(h.t.packed[1] == TBL_DELETED && h.t.keys[1] == ks[mid]);
+  EXPECT(table_get(h.t, ks[mid]) == TBL_EMPTY);
+  EXPECT(table_find(h.t, ks[mid], &s) == TBL_DELETED && s == 1);
+  for (size_t i = 0; i < ks.size(); i++)
+    if (i != mid) EXPECT(table_get(h.t, ks[i]) == value_of(ks[i], i));
+  EXPECT(table_find(h.t, absent, &s) == TBL_EMPTY && s == 8);  // past the deleted slot, to the first empty one
+  EXPECT(table_get(h.t, absent) == TBL_EMPTY);
+  // revive: its own slot again, no new one
+  const uint64_t before = h.non_empty();
+  EXPECT(before == ks.size() && before == h.used);
+  EXPECT(h.put(ks[mid], value_of(ks[mid], 99), &s) && s == 1);
+  EXPECT(h.non_empty() == before && h.used == before);
+  EXPECT(table_get(h.t, ks[mid]) == value_of(ks[mid], 99));
+  // 0 and 2^64 - 1 are ordinary keys
+  for (uint64_t k : {0ull, ~0ull}) {
+    EXPECT(table_get(h.t, k) == TBL_EMPTY);
+    EXPECT(h.put(k, value_of(k, 7)));
+    EXPECT(table_get(h.t, k) == value_of(k, 7));
+    h.del(k);
+    EXPECT(table_get(h.t, k) == TBL_EMPTY);
+    EXPECT(h.put(k, value_of(k, 8)) && table_get(h.t, k) == value_of(k, 8));
+  }
+  EXPECT(h.non_empty() == before + 2);
+}
+
+static void full_check(uint64_t cap) {
+  HostTable h(cap / 2);
+  EXPECT(h.cap() == cap);
+  std::vector<uint64_t> ks;
+  for (uint64_t i = 0; i < cap / 2; i++) {
+    ks.push_back(rnd());
+    EXPECT(h.put(ks.back(), value_of(ks.back(), i)));
+  }
+  EXPECT(h.used == cap / 2 && h.non_empty() == cap / 2);
+  EXPECT(table_admits(h.used, 0, h.t.log2cap) && !table_admits(h.used, 1, h.t.log2cap));
+  EXPECT(!h.put(rnd(), 1));                         // a new key is refused ...
+  EXPECT(h.put(ks[0], value_of(ks[0], 12345)));     // ... an update is not,
+  h.del(ks[1]);
+  EXPECT(!h.put(rnd(), 1));                         // a delete frees no slot,
+  EXPECT(h.put(ks[1], value_of(ks[1], 777)));       // and the deleted key comes back
+  EXPECT(h.non_empty() == cap / 2);
+}
+
+static void random_run(uint64_t cap, uint64_t seed) {
+  rng_state = seed;
+  HostTable h(cap / 2);
+  EXPECT(h.cap() == cap);
+  std::vector<uint64_t> universe = {0ull, ~0ull};
+  while (universe.size() < cap) universe.push_back(rnd());  // twice what the table admits
+  std::unordered_map<uint64_t, uint64_t> live;
+  std::unordered_set<uint64_t> ever;
+  uint64_t refused = 0;
+  for (int op = 0; op < 10000; op++) {
+    const uint64_t k = universe[rnd() % universe.size()];
+    switch (rnd() % 4) {
+      case 0:
+      case 1: {  // insert / update
+        const uint64_t v = value_of(k, rnd());
+        const bool fits = ever.count(k) || ever.size() < cap / 2;
+        const bool ok = h.put(k, v);
+        EXPECT(ok == fits);
+        if (ok) { live[k] = v; ever.insert(k); } else refused++;
+        break;
+      }
+      case 2:
+        h.del(k);
+        live.erase(k);
+        break;
+      default: {
+        const auto it = live.find(k);
+        EXPECT(table_get(h.t, k) == (it == live.end() ? TBL_EMPTY : it->second));
+      }
+    }
+    EXPECT(h.used == ever.size() && h.used <= cap / 2);
+    if (op % 500 == 499 || op == 9999) {
+      EXPECT(h.non_empty() == ever.size());
+      for (uint64_t q : universe) {
+        const auto it = live.find(q);
+        EXPECT(table_get(h.t, q) == (it == live.end() ? TBL_EMPTY : it->second));
+      }
+    }
+  }
+  EXPECT(ever.size() == cap / 2 && refused > 0);  // the run reached the bound and met the refusal
+}
+
+static void size_check() {
+  for (uint64_t n : {0ull, 1ull, 32ull, 33ull, 1ull << 20, (1ull << 20) + 1}) {
+    uint64_t want = 64;
+    while (want < 2 * n) want *= 2;
+    EXPECT(table_capacity(n) == want && (want & (want - 1)) == 0 && want >= 64 && want >= 2 * n);
+    EXPECT(want == 64 || want / 2 < 2 * n);
+    EXPECT(table_bytes_for(n) == 16 * want);
+    EXPECT((1ull << table_log2cap(table_bytes_for(n))) == want);
+  }
+  // byte counts that are no power of two round down
+  EXPECT(table_log2cap(16 * 64) == 6 && table_log2cap(16 * 64 + 8) == 6 && table_log2cap(16 * 127) == 6);
+  EXPECT(table_log2cap(16 * 128) == 7 && table_log2cap(16 * 128 - 1) == 6);
+  uint64_t word = 0;
+  EXPECT(table_ok(&word, 16 * 64) && !table_ok(&word, 16 * 64 - 1) && !table_ok(&word, 0));
+  EXPECT(!table_ok(nullptr, 16 * 64));
+  std::vector<uint64_t> mem(2 * 127);
+  const Table t = table_view(mem.data(), mem.size() * 8);
+  EXPECT(t.log2cap == 6 && t.keys == mem.data() && t.packed == mem.data() + 64);
+}
+
+int main() {
+  chain_check();
+  for (uint64_t cap : {64ull, 1024ull}) {
+    full_check(cap);
+    random_run(cap, 0xC0FFEE + cap);
+  }
+  size_check();
+  if (g_fail) {
+    fprintf(stderr, "table_check: %d checks failed\n", g_fail);
+    return 1;
+  }
+  printf("table_check ok\n");
+  return 0;
+}

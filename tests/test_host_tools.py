@@ -61,6 +61,20 @@ def test_finalize_rule_sanitized():
     assert p.returncode == 0 and "fin_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
 
 
+def test_index_table_rule_sanitized():
+    """csrc/srd_table.h (the device index table: probe, claim, slot states, size arithmetic -- the code the table's
+    kernels run, the claim's CAS as a plain compare-and-store) as a stand-alone host program under ASan + UBSan,
+    single-threaded against a std::unordered_map: a probe chain of 12 keys that wraps from slot 63 to slot 0, a
+    delete in its middle and the revival into the same slot, key hashes 0 and 2^64 - 1, an absent key's probe past
+    deleted slots, seeded runs of 10 000 operations at capacities 64 and 1024 that reach capacity / 2 non-empty slots
+    and meet the refusal there, and the capacity / log2cap / table_ok arithmetic (tests/sanitize/table_check.cpp)."""
+    d = os.path.join(ROOT, "tests", "sanitize")
+    subprocess.check_call(["make", "-s", "-C", d, "build/table_check"])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    p = subprocess.run([os.path.join(d, "build", "table_check")], capture_output=True, text=True, env=env, timeout=600)
+    assert p.returncode == 0 and "table_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
+
+
 def _abi_check_bin():
     d = os.path.join(ROOT, "tests", "abi_c")
     if not os.path.exists(S.LIB_PATH):
