@@ -647,6 +647,54 @@ int srd_payload_gather_device(srd_ctx *ctx, const uint8_t *d_file, uint64_t file
                               uint32_t *d_crc_computed /* n, nullable */,
                               uint64_t *total, void *stream);
 
+/* ---- payloads already in HBM appended to a store ----
+ *   srd_batch_append_device <- DataStoreWriter::batch_write_with_key_hashes(.., false)
+ *                              (data_store.rs:847-939) for payloads that are
+ *                              device ranges, = n write_stream_with_key_hash
+ *                              calls (:758-825); what copy / transfer / rename
+ *                              (:941-984) run on
+ * d_src_off / d_len are n ranges [off, off + len) inside d_payloads[0 ..
+ * payloads_len); d_file[j] = file byte j, writable to file_cap bytes, 16-byte
+ * aligned.  With P_0 = roundup64(tail): entry i's payload lies at P_i, its
+ * metadata {key_hash, prev_offset, crc32(payload)} at m_i = P_i + len_i,
+ * prev_offset_0 = tail, prev_offset_i = m_(i-1) + 20, P_(i+1) = roundup64(m_i +
+ * 20), *new_tail = m_(n-1) + 20; the bytes [tail, P_0) and [m_i + 20, P_(i+1))
+ * are zero.  d_meta_off_out[i] = m_i: with d_key_hashes, the pairs
+ * srd_index_table_apply_device takes as they are (the call itself does not
+ * touch any index table).  No byte below tail changes, none at or above
+ * roundup64(*new_tail) is touched, and [*new_tail, roundup64(*new_tail)) is
+ * left alone or written as zero.  Any source alignment gives the right bytes;
+ * 16-byte-aligned sources are the fast path.  No tombstones (deletes:
+ * srd_batch_delete_hashed_device).  n == 0: *new_tail = tail, nothing runs.
+ * SRD_ERR_ARG with the reference's message, nothing written to d_file or
+ * d_meta_off_out, *new_tail = tail: a length of 0 ("Payload cannot be
+ * empty."); a payload that is the single byte 0 ("NULL-byte payloads cannot be
+ * written directly."; the only payload byte the layout reads); a range not
+ * inside [0, payloads_len) (judged without wrap, never dereferenced); a new
+ * tail of 2^48 or more; srd_padded_size(new tail) > file_cap (the message names
+ * file_cap); d_payloads[0 .. payloads_len) overlapping d_file[tail ..
+ * roundup64(new tail)); n >= 2^31; 2^32 or more work units (chunks of
+ * SRD_GATHER_CHUNK bytes of one entry).  With several refused entries the
+ * first in batch order decides the message.
+ * SRD_APPEND_STREAM_RULE adds write_stream's check (data_store.rs:783-797): a
+ * payload of any length whose bytes are all 0 fails the call with
+ * "NULL-byte-only streams cannot be written directly." -- known only after
+ * the bytes have been streamed, as in the reference: bytes at or above tail
+ * and d_meta_off_out may have been written, *new_tail = tail, and the
+ * caller's tail and index do not move.
+ * Ordered on `stream`; waits once, for the error word, the new tail and the
+ * unit counts, and returns with the copy enqueued: later work on `stream`
+ * sees the store and d_meta_off_out.  With SRD_APPEND_STREAM_RULE the call
+ * waits a second time, for the kernels, before it returns.  The workspace
+ * comes from the context (srd_ctx_device_bytes counts it). */
+#define SRD_APPEND_STREAM_RULE 1u
+int srd_batch_append_device(srd_ctx *ctx, const uint8_t *d_payloads, uint64_t payloads_len,
+                            const uint64_t *d_src_off, const uint64_t *d_len,
+                            const uint64_t *d_key_hashes, uint64_t n, uint32_t flags,
+                            uint64_t tail, uint8_t *d_file, uint64_t file_cap,
+                            uint64_t *new_tail, uint64_t *d_meta_off_out /* n */,
+                            void *stream);
+
 /* Synthetic store of the BASELINE configs written on the device (the
  * checksum-on-append writer of data_store.rs:847-939 for keys
  * "bench-key-{i}" and counter-mode splitmix64 payloads).  lens==NULL ->

@@ -13,6 +13,8 @@
 //     srd_writer.hip          batch writer
 //     srd_gather.h            the payload gather's range rule, unit / chunk arithmetic and CRC combine (a CPU check uses it too)
 //     srd_gather.hip          verified payloads: batched gather with checksum check (uses the writer's helpers)
+//     srd_append.h            the device append's range rule, layout and refusals (a CPU check uses it too)
+//     srd_append.hip          payloads in HBM appended to a store: layout and finish around the gather's kernels
 //     srd_table.h             the lookup table's rule: slot states, probe, claim, size arithmetic (the host entries
 //                             and a CPU check use it too)
 //     srd_index.hip           lookup table build and reads, iterator, compaction
@@ -29,7 +31,7 @@
 //     srd_host_input.hip      staging, pinned host results, host-pointer entries
 //     srd_multi.hip           multi-GPU open
 //     srd_ops.hip             probe, batch digests, synth, writer, table / reads / maintenance, iterator,
-//                             compaction, payload gather
+//                             compaction, payload gather, device append
 //   this file               error / build-info entries, stamps read-outs, host self-test
 //
 // Glue scans/compactions use hipCUB (library primitives, like calling
@@ -59,6 +61,8 @@
 #include "srd_writer.hip"
 #include "srd_gather.h"
 #include "srd_gather.hip"
+#include "srd_append.h"
+#include "srd_append.hip"
 #include "srd_table.h"
 #include "srd_index.hip"
 #include "srd_index_live.hip"

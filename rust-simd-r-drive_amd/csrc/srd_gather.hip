@@ -22,6 +22,9 @@
 //                           single-unit hit's CRC is finished here)
 //   payload_combine_kernel  one wave per multi-unit hit: folds its chunks' CRCs
 //   payload_finish_kernel   per query: stored checksum, status, the caller's arrays
+// srd_batch_append_device (srd_append.hip) runs the units, gather and combine
+// kernels as they are, with the caller's blob as the file and the store as the
+// output.
 
 namespace srd {
 
@@ -47,6 +50,7 @@ struct PayloadGatherArgs {
   uint8_t* o_status;
   uint32_t* o_crc;
   uint32_t layout_only;
+  uint32_t* nz;    // [n] payload_gather_kernel<true>: set for a hit with a byte that is not 0
 };
 
 __global__ __launch_bounds__(256) void payload_layout_kernel(PayloadGatherArgs a) {
@@ -82,6 +86,10 @@ __global__ __launch_bounds__(256) void payload_units_kernel(PayloadGatherArgs a)
 // unaligned piece takes the byte path.  Nothing outside the unit's own
 // payload bytes is read: whole pieces lie inside the chunk, the byte path
 // stops at its end.
+// NZ (srd_batch_append_device's stream rule; the gather runs NZ = false): the
+// unit also ORs its words, as write_kernel does for its null_only word, and a
+// unit with a byte that is not 0 marks its hit in a.nz.
+template <bool NZ = false>
 __global__ __launch_bounds__(SCAN_WAVES_V2 * 64, 1) void payload_gather_kernel(PayloadGatherArgs a) {
   __shared__ ScanLds lds;
   load_crc_lds<true>(lds);
@@ -139,7 +147,7 @@ __global__ __launch_bounds__(SCAN_WAVES_V2 * 64, 1) void payload_gather_kernel(P
 
   uint64_t u = w, b = 0;
   Unit x = unit_s(u);
-  uint32_t acc = 0;
+  uint32_t acc = 0, any = 0;
   auto step = [&](uint32_t (&d)[16], uint32_t (&nx)[16]) -> bool {
     const uint64_t nb = (x.clen + TILE - 1) / TILE;
     // the block after (u, b); past the wave's last unit: block 0 of this unit again (harmless)
@@ -188,6 +196,11 @@ __global__ __launch_bounds__(SCAN_WAVES_V2 * 64, 1) void payload_gather_kernel(P
         __builtin_amdgcn_raw_buffer_store_b128(u32x4{d[4 * j], d[4 * j + 1], d[4 * j + 2], d[4 * j + 3]}, rb,
                                                vp[j] && copy ? 16u * lane + 1024u * j : OOB_OFF, 0, 0);
     }
+    if constexpr (NZ) {
+      if (b == 0) any = 0;
+#pragma unroll
+      for (int j = 0; j < 16; j++) any |= d[j];
+    }
     // raw CRC of this 4 KiB block (zero-padded past the chunk)
     const uint32_t hx = half_suffix_xor(lane_weight_or(crc_line4_wide(d, lds, R), nib_lane), lane);
     const uint32_t lo = __builtin_amdgcn_readlane(hx, 0), hi = __builtin_amdgcn_readlane(hx, 32);
@@ -210,6 +223,9 @@ __global__ __launch_bounds__(SCAN_WAVES_V2 * 64, 1) void payload_gather_kernel(P
     // -- and, behind a hit's last chunk, the zero bytes up to the 64-byte boundary
     __builtin_amdgcn_raw_buffer_store_b32(val, out_rsrc(a.crc + x.hit, done && x.single ? 4u : 0u), 4u * lane, 0, 0);
     __builtin_amdgcn_raw_buffer_store_b32(val, out_rsrc(a.raw + u, done && !x.single ? 4u : 0u), 4u * lane, 0, 0);
+    if constexpr (NZ)  // (every unit of a hit that stores here stores the same word)
+      __builtin_amdgcn_raw_buffer_store_b32(1u, out_rsrc(a.nz + x.hit, done && __ballot(any != 0) ? 4u : 0u), 4u * lane, 0,
+                                            0);
     const uint32_t nz = done && x.last && copy ? (uint32_t)(gather_pad64(x.hlen) - x.hlen) : 0u;
     __builtin_amdgcn_raw_buffer_store_b8((uint8_t)0, out_rsrc(a.out + x.dst + x.clen, nz), (uint32_t)lane, 0, 0);
     u = u2;

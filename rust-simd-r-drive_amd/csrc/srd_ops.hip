@@ -1,7 +1,7 @@
 // srd_ops.hip -- host launch code of the remaining kernel families (included
 // by srd_api.hip): stream probe, batch digests, synth, batch writer, device
 // lookup table, batched reads and the table's maintenance, iterator and
-// compaction.
+// compaction, payload gather, device append.
 
 // A device allocation / an event that lasts for one call, released on every return path
 // (no workspace buffer: as large as the caller's input, the context would keep and report it)
@@ -714,5 +714,127 @@ extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint
   }
   payload_finish_kernel<<<grid_for(n + 1), 256, 0, s>>>(a);
   LAUNCHED(s, "payload_finish_kernel");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Payloads already in HBM appended to a store (srd_append.hip): layout, one
+// wait for the error word, the new tail and the unit counts, then the gather's
+// unit table, streaming kernel and combine with the store as their output,
+// and the finish enqueued on the stream
+extern "C" int srd_batch_append_device(srd_ctx* c, const uint8_t* d_payloads, uint64_t payloads_len,
+                                       const uint64_t* d_src_off, const uint64_t* d_len, const uint64_t* d_key_hashes,
+                                       uint64_t n, uint32_t flags, uint64_t tail, uint8_t* d_file, uint64_t file_cap,
+                                       uint64_t* new_tail, uint64_t* d_meta_off_out, void* stream) {
+  if (!c || !new_tail || (flags & ~SRD_APPEND_STREAM_RULE) || ((uintptr_t)d_file & 15) ||
+      (n && (!d_src_off || !d_len || !d_key_hashes || !d_file || !d_meta_off_out || (payloads_len && !d_payloads)))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  *new_tail = tail;
+  if (n >= (1ull << 31)) { set_err("too many entries in one batch"); return SRD_ERR_ARG; }
+  if (!n) return 0;
+  const bool rule = flags & SRD_APPEND_STREAM_RULE;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream_of(c, stream);
+  TRY(ensure(c, B_GA_PLEN, n * 8));
+  TRY(ensure(c, B_GA_CHK, n * 8));
+  TRY(ensure(c, B_GA_OFF, n * 8));
+  TRY(ensure(c, B_GA_CPRE, n * 8));
+  TRY(ensure(c, B_GA_CRC, n * 4));
+  TRY(ensure(c, B_GA_CNT, 64));
+  TRY(ensure(c, B_AP_END, n * 8));
+  if (rule) TRY(ensure(c, B_AP_NZ, n * 4));
+  TRY(ensure_scan(c, (const uint64_t*)nullptr, (uint64_t*)nullptr, n));  // both scans below
+  AppendArgs a{};
+  a.pay = d_payloads;
+  a.pay_len = payloads_len;
+  a.src = d_src_off;
+  a.len = d_len;
+  a.kh = d_key_hashes;
+  a.n = n;
+  a.tail = tail;
+  a.base = append_base(tail);
+  a.end = P<uint64_t>(c, B_AP_END);
+  a.slot = P<uint64_t>(c, B_GA_PLEN);
+  a.chk = P<uint64_t>(c, B_GA_CHK);
+  a.pre = P<uint64_t>(c, B_GA_OFF);
+  a.cnt = P<unsigned long long>(c, B_GA_CNT);
+  a.crc = P<uint32_t>(c, B_GA_CRC);
+  a.nz = rule ? P<uint32_t>(c, B_AP_NZ) : nullptr;
+  a.file = d_file;
+  a.mo = d_meta_off_out;
+  HIPCHK(hipMemsetAsync(a.cnt, 0, 40, s));
+  HIPCHK(hipMemsetAsync(a.cnt + 1, 0xFF, 8, s));  // the error word: none
+  if (rule) HIPCHK(hipMemsetAsync(P<void>(c, B_AP_NZ), 0, n * 4, s));
+  append_layout_kernel<<<grid_for(n), 256, 0, s>>>(a);
+  LAUNCHED(s, "append_layout_kernel");
+  // everything the host decides on, on one wait (n < 2^31 fits hipCUB's int count)
+  uint64_t pre_last = 0, units = 0;
+  struct { unsigned long long n_multi, err, coarse, len_last; } h{};
+  TRY(scan_sum(c, (const uint64_t*)a.slot, P<uint64_t>(c, B_GA_OFF), n, s));
+  TRY(scan_sum_total(c, (const uint64_t*)a.chk, P<uint64_t>(c, B_GA_CPRE), n, s, &units, rd(a.pre + n - 1, &pre_last),
+                     SmallRead{a.cnt, &h, sizeof h}));
+  if (h.err != ~0ull) {
+    const uint32_t st = append_err_status(h.err);
+    set_err(st == APPEND_EMPTY       ? "Payload cannot be empty."
+            : st == APPEND_NULL_BYTE ? "NULL-byte payloads cannot be written directly."
+            : st == APPEND_BAD_RANGE ? "payload range " + std::to_string(h.err >> 8) + " does not lie inside d_payloads"
+                                     : "the batch would end at 2^48 or beyond (the index packs 48-bit offsets)");
+    return SRD_ERR_ARG;
+  }
+  uint64_t nt = 0;
+  if (!append_new_tail(tail, h.coarse, pre_last, h.len_last, &nt)) {
+    set_err("the batch would end at 2^48 or beyond (the index packs 48-bit offsets)");
+    return SRD_ERR_ARG;
+  }
+  if (srd_padded_size(nt) > file_cap) {
+    set_err("file_cap too small for the batch: it ends at " + std::to_string(nt));
+    return SRD_ERR_ARG;
+  }
+  {  // the blob may not lie in what the call writes
+    const uintptr_t p0 = (uintptr_t)d_payloads, p1 = p0 + payloads_len;
+    const uintptr_t w0 = (uintptr_t)d_file + tail, w1 = (uintptr_t)d_file + gather_pad64(nt);
+    if (payloads_len && p0 < w1 && w0 < p1) { set_err("d_payloads overlaps the bytes the batch writes"); return SRD_ERR_ARG; }
+  }
+  if (units >= (1ull << 32)) { set_err("too many work units in one batch"); return SRD_ERR_ARG; }
+  TRY(ensure(c, B_GA_UNIT, units * 4));
+  TRY(ensure(c, B_GA_RAW, units * 4));
+  // the gather's kernels: the blob is their file, the store from base on their
+  // output, the layout's prefix their output offsets (64-aligned: base + pre)
+  PayloadGatherArgs ga{};
+  ga.file = d_payloads;
+  ga.flen = payloads_len;
+  ga.start = d_src_off;
+  ga.end = a.end;
+  ga.n = n;
+  ga.chk = a.chk;
+  ga.off = P<uint64_t>(c, B_GA_OFF);
+  ga.cpre = P<uint64_t>(c, B_GA_CPRE);
+  ga.unit_hit = P<uint32_t>(c, B_GA_UNIT);
+  ga.n_units = units;
+  ga.raw = P<uint32_t>(c, B_GA_RAW);
+  ga.crc = P<uint32_t>(c, B_GA_CRC);
+  ga.out = d_file + a.base;
+  ga.nz = P<uint32_t>(c, B_AP_NZ);
+  payload_units_kernel<<<grid_for(units), 256, 0, s>>>(ga);
+  LAUNCHED(s, "payload_units_kernel");
+  const unsigned g = (unsigned)std::min<uint64_t>((units + SCAN_WAVES_V2 - 1) / SCAN_WAVES_V2, c->scan_blocks);
+  if (rule) payload_gather_kernel<true><<<g, SCAN_WAVES_V2 * 64, 0, s>>>(ga);
+  else payload_gather_kernel<<<g, SCAN_WAVES_V2 * 64, 0, s>>>(ga);
+  LAUNCHED(s, "payload_gather_kernel");
+  if (h.n_multi) payload_combine_kernel<<<(unsigned)std::min<uint64_t>((n + 3) / 4, 4096), 256, 0, s>>>(ga);
+  LAUNCHED(s, "payload_combine_kernel");
+  append_finish_kernel<<<(unsigned)std::min<uint64_t>((n + 255) / 256, 4096), 256, 0, s>>>(a);
+  LAUNCHED(s, "append_finish_kernel");
+  if (rule) {  // write_stream's check comes after the bytes (data_store.rs:783-797): the second wait
+    unsigned long long null_only = 0;
+    TRY(read_small(c, s, {rd(a.cnt + 4, &null_only)}));
+    if (null_only) {
+      set_err("NULL-byte-only streams cannot be written directly.");
+      return SRD_ERR_ARG;
+    }
+  }
+  *new_tail = nt;
   return 0;
 }

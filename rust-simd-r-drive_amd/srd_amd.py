@@ -71,7 +71,7 @@ EXPORTS = [
     "srd_validate_index_multi_device", "srd_ctx_multi_summary", "srd_ctx_scan_list", "srd_ctx_set_timing_every",
     "srd_stream_probe_device", "srd_ctx_multi_shard_ms",
     "srd_index_table_apply_device", "srd_index_table_export_device", "srd_batch_delete_hashed_device",
-    "srd_payload_gather_device",
+    "srd_payload_gather_device", "srd_batch_append_device",
 ]
 
 
@@ -201,6 +201,7 @@ def lib():
                                                      C.POINTER(u64), C.POINTER(u64)]
         L.srd_payload_gather_device.argtypes = [vp, vp, u64, vp, vp, u64, u32, vp, u64, vp, vp, vp,
                                                 C.POINTER(u64), vp]
+        L.srd_batch_append_device.argtypes = [vp, vp, u64, vp, vp, vp, u64, u32, u64, vp, u64, C.POINTER(u64), vp, vp]
         L.srd_iter_entries_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
         L.srd_estimate_compaction_savings_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.srd_compact_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, vp]
@@ -955,6 +956,28 @@ def gather_ranges(d_file: int, file_len: int, st, en, flags: int = 0, ctx: "Cont
     return GatherResult(data, o, ln, s, crc[:n].cpu().numpy().view(np.uint32))
 
 
+APPEND_STREAM_RULE = 1  # SRD_APPEND_STREAM_RULE: write_stream's refusal of NULL-byte-only payloads
+
+
+def batch_append_device(d_payloads: int, payloads_len: int, d_src_off: int, d_len: int, d_key_hashes: int, n: int,
+                        flags: int, tail: int, d_file: int, file_cap: int, d_meta_off_out: int,
+                        ctx: "Context | None" = None, stream: int | None = None) -> int:
+    """srd_batch_append_device as it is (device pointers in, the new tail out):
+    ordered on `stream` (default: the context stream), returns with the copy
+    enqueued.  SrdError carries the refusal's message and `.rc`."""
+    ctx = ctx or default_ctx()
+    nt = C.c_uint64()
+    rc = lib().srd_batch_append_device(ctx.h, C.c_void_p(d_payloads), payloads_len, C.c_void_p(d_src_off),
+                                       C.c_void_p(d_len), C.c_void_p(d_key_hashes), n, flags, tail, C.c_void_p(d_file),
+                                       file_cap, C.byref(nt), C.c_void_p(d_meta_off_out),
+                                       C.c_void_p(stream if stream is not None else ctx.stream))
+    if rc != 0:
+        e = SrdError(f"srd error {rc}: {lib().srd_last_error().decode()}")
+        e.rc = rc
+        raise e
+    return int(nt.value)
+
+
 class DeviceIndex:
     """The KeyIndexer adopted on the GPU: an open-addressing table in HBM built
     from n unique (key_hash, packed) device pairs -- e.g. the index arrays of a
@@ -1293,6 +1316,128 @@ class DeviceStore:
         self.index.apply(d_kh, d_mo, tomb if tomb.any() else None)  # same stream: behind the writer; waits
         self._tail = new_tail
         return new_tail
+
+    # -- writes of payloads that are already on the device ----------------------------------
+
+    def _append_device(self, d_hashes, blob_ptr: int, blob_len: int, d_offs, d_lens, flags: int) -> int:
+        """srd_batch_append_device on the context stream (§10's stream rule), then
+        the reindex of its (key_hash, offset) pairs, then the tail.  Any error
+        leaves the tail and the index as they were."""
+        import torch
+        n = d_hashes.numel()
+        d_mo = torch.empty(n, dtype=torch.int64, device=self.buf.device)
+        self.index._lib_after_torch()
+        try:
+            new_tail = batch_append_device(blob_ptr, blob_len, d_offs.data_ptr(), d_lens.data_ptr(), d_hashes.data_ptr(), n,
+                                           flags, self._tail, self.buf.data_ptr(), self.buf.numel(), d_mo.data_ptr(),
+                                           self.ctx)
+        except SrdError as e:
+            self.index._sync_lib()  # (the inputs may be temporaries of the caller)
+            if e.rc == SRD_ERR_ARG and "file_cap" in str(e):
+                raise ValueError("the batch ends beyond the store's capacity") from e
+            raise
+        self.index.apply(d_hashes, d_mo)  # same stream: behind the append; waits
+        self._tail = new_tail
+        return new_tail
+
+    def batch_write_device_with_key_hashes(self, hashes, blob, offs, lens, stream_rule: bool = False) -> int:
+        """batch_write_with_key_hashes(.., false) (data_store.rs:847-939) for
+        payloads that already lie in HBM: entry i is blob[offs[i] : offs[i] +
+        lens[i]] (`blob`: a contiguous uint8 tensor on the store's device; hashes,
+        offs, lens: host sequences or device int64 tensors).  The layout, the copy
+        and the checksums run on the device (srd_batch_append_device), then the
+        reindex.  Returns the new tail.  stream_rule adds write_stream's refusal of
+        payloads that are all NULL bytes.  A batch beyond the capacity raises
+        ValueError, the other refusals SrdError with the reference's message; the
+        tail and the index are unchanged then."""
+        import torch
+        if not isinstance(blob, torch.Tensor) or blob.dtype != torch.uint8 or blob.device != self.buf.device or \
+                not blob.is_contiguous():
+            raise ValueError("blob must be a contiguous uint8 tensor on the store's device")
+        _same_len(hashes, offs, "key hashes and payload offsets")
+        _same_len(hashes, lens, "key hashes and payload lengths")
+        if not len(hashes):
+            return self._tail
+        as_dev = self.index._as_dev
+        return self._append_device(as_dev(hashes), blob.data_ptr(), blob.numel(), as_dev(offs), as_dev(lens),
+                                   APPEND_STREAM_RULE if stream_rule else 0)
+
+    def batch_write_device(self, keys, blob, offs, lens) -> int:
+        """batch_write (data_store.rs:838-843) for payloads in HBM: compute_hash_batch,
+        then batch_write_device_with_key_hashes."""
+        _same_len(keys, offs, "keys and payloads")
+        if not len(keys):
+            return self._tail
+        return self.batch_write_device_with_key_hashes(compute_hash_batch(keys, self.ctx), blob, offs, lens)
+
+    # -- copy / transfer / rename (data_store.rs:941-984): write_stream of the read entry ---
+
+    def _entries_of(self, keys, missing: str):
+        """The payload ranges of `keys` as device tensors (hashes, start, length),
+        every read verified by its key's own tag; KeyError for a key that reads as None."""
+        keys = [bytes(k) for k in keys]
+        if len(set(keys)) != len(keys):
+            raise ValueError("Duplicate keys in one batch.")
+        h = compute_hash_batch(keys, self.ctx)
+        st, en, _keep = self.index._ranges_device(self.buf.data_ptr(), self._tail, h, h)
+        self.index._sync_lib()
+        hs, he = st.cpu().numpy(), en.cpu().numpy()
+        for k, a, b in zip(keys, hs, he):
+            if a == b:
+                raise KeyError(f"{missing}: {k!r}")
+        return _keep[0], st, en - st
+
+    def _append_from(self, src: "DeviceStore", d_hashes, st, lens) -> int:
+        """write_stream_with_key_hash of src's entries at [st, st + lens) into this
+        store (copy_handle, data_store.rs:587-590): the checksums are recomputed,
+        NULL-byte-only payloads refused.  Runs on this store's context, after
+        src's context stream."""
+        import torch
+        if src.buf.device != self.buf.device:
+            raise ValueError("both stores must be on one device")
+        dev = self.buf.device
+        torch.cuda.ExternalStream(self.ctx.stream, device=dev).wait_stream(
+            torch.cuda.ExternalStream(src.ctx.stream, device=dev))
+        return self._append_device(d_hashes, src.buf.data_ptr(), src._tail, st, lens, APPEND_STREAM_RULE)
+
+    def batch_copy(self, keys, target: "DeviceStore") -> int:
+        """copy (data_store.rs:960-979) of every key: the entries appended to
+        `target` under their key hashes.  Returns target's new tail."""
+        if target is self or target.buf.data_ptr() == self.buf.data_ptr():
+            raise ValueError("Cannot copy entry to the same storage. Use `rename` instead.")
+        if not len(keys):
+            return target._tail
+        h, st, lens = self._entries_of(keys, "Key not found")
+        return target._append_from(self, h, st, lens)
+
+    def batch_transfer(self, keys, target: "DeviceStore") -> int:
+        """transfer (data_store.rs:981-984): copy, then delete here.  Returns this store's new tail."""
+        self.batch_copy(keys, target)
+        return self.batch_delete(keys) if len(keys) else self._tail
+
+    def batch_rename(self, old_keys, new_keys) -> int:
+        """rename (data_store.rs:941-958) of every pair: the old entries appended
+        under the new keys' hashes, then the old keys deleted.  Returns the new tail."""
+        _same_len(old_keys, new_keys, "old and new keys")
+        old_keys, new_keys = [bytes(k) for k in old_keys], [bytes(k) for k in new_keys]
+        if any(a == b for a, b in zip(old_keys, new_keys)):
+            raise ValueError("Cannot rename a key to itself")
+        if len(set(new_keys)) != len(new_keys) or set(new_keys) & set(old_keys):
+            raise ValueError("Duplicate keys in one batch.")
+        if not old_keys:
+            return self._tail
+        _h, st, lens = self._entries_of(old_keys, "Old key not found")
+        self._append_from(self, self.index._as_dev(compute_hash_batch(new_keys, self.ctx)), st, lens)
+        return self.batch_delete(old_keys)
+
+    def copy(self, key: bytes, target: "DeviceStore") -> int:
+        return self.batch_copy([key], target)
+
+    def transfer(self, key: bytes, target: "DeviceStore") -> int:
+        return self.batch_transfer([key], target)
+
+    def rename(self, old_key: bytes, new_key: bytes) -> int:
+        return self.batch_rename([old_key], [new_key])
 
     def batch_delete(self, keys) -> int:
         """DataStoreWriter::batch_delete (data_store.rs:990-993)."""
