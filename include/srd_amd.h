@@ -24,6 +24,9 @@
  *   srd_xxh3_64_batch(_device) <- compute_hash_batch
  *                                src/storage_engine/digest/compute_hash.rs:64-77
  *   srd_xxh3_64               <- compute_hash  (compute_hash.rs:25-27)
+ *   srd_compact_live_device   <- DataStore::compact
+ *                                src/storage_engine/data_store.rs:706-749
+ *                                over a live session's store and index
  *
  * Semantics (bit-exact with the reference):
  *   - final_len = largest tail t <= file_len whose backward chain is
@@ -694,6 +697,75 @@ int srd_batch_append_device(srd_ctx *ctx, const uint8_t *d_payloads, uint64_t pa
                             uint64_t tail, uint8_t *d_file, uint64_t file_cap,
                             uint64_t *new_tail, uint64_t *d_meta_off_out /* n */,
                             void *stream);
+
+/* ---- a live session compacted on the device, its index carried over ----
+ *   srd_compact_live_device <- DataStore::compact (data_store.rs:706-749) over
+ *                              iter_entries (:276-280) / EntryIterator
+ *                              (entry_iterator.rs:69-126), each entry written
+ *                              by copy_handle (:587-590), which is
+ *                              write_stream_with_key_hash (:758-825)
+ * d_table is the live table of the store d_file[0 .. file_len) (as
+ * srd_index_table_build_device / _apply_device / srd_batch_delete_hashed_device
+ * leave it); both are only read.  The entries written are the table's live
+ * pairs -- what srd_index_table_export_device gives, removed keys are absent --
+ * that pass par_iter_entries' filter (a key whose indexed entry is a tombstone
+ * on disk is dropped), newest first: the order of srd_iter_entries_device over
+ * the export.  No trip through a validate pass, and the pairs never leave the
+ * device.
+ * d_out[0 .. new_len) is exactly what srd_batch_append_device(..,
+ * SRD_APPEND_STREAM_RULE, tail = 0, ..) writes for those payload ranges in that
+ * order (its comment above is the layout rule: P_0 = 0, P_(i+1) = roundup64(m_i
+ * + 20), metadata {key_hash, prev_offset, crc32(payload)}, zero prepads; the
+ * checksum is recomputed) -- byte for byte what srd_compact_device writes for
+ * the same index.  No byte at or above roundup64(new_len) is touched, and
+ * [new_len, roundup64(new_len)) is left alone or written as zero.  d_out must
+ * be 16-byte aligned.
+ * d_new_table (new_table_bytes >= srd_index_table_bytes(n_entries)) receives
+ * the table srd_index_table_build_device would build from the n_entries pairs
+ * (key_hash, pack(key_hash >> 48, new metadata offset)): its `used` count is
+ * n_entries, no slot is deleted.
+ * A written entry whose recomputed CRC-32 differs from the checksum stored in
+ * the source (the little-endian u32 at d_file[end + 16 .. end + 20)) is copied
+ * faithfully, as the reference would, gets the recomputed checksum, and counts
+ * into n_crc_bad: a bad CRC is data, never an error -- the caller decides.
+ * d_out == NULL is a planning call: n_entries, new_len and kept_bytes only,
+ * nothing is written, d_new_table is ignored.
+ * SRD_ERR_ARG, nothing written to d_out or d_new_table, n_entries / kept_bytes
+ * / new_len still reported where they are known (the first three cases below:
+ * nothing has run, they are 0):
+ *   d_out not 16-byte aligned;
+ *   [d_out, d_out + out_cap) or [d_new_table, d_new_table + new_table_bytes)
+ *     overlapping the store's padded range (srd_padded_size(file_len)), the old
+ *     table, or each other;
+ *   a NULL stats, a table_bytes below the smallest table;
+ *   srd_padded_size(new_len) > out_cap (the store the call leaves is one the
+ *     validate and append calls can take as it is: they need that slack);
+ *   new_table_bytes < srd_index_table_bytes(n_entries);
+ *   the append's own bounds: 2^31 or more entries, 2^32 or more work units, a
+ *     new length of 2^48 or more.
+ * A kept payload whose bytes are all 0 fails the call with the reference's
+ * "NULL-byte-only streams cannot be written directly." (as srd_compact_device
+ * and the stream rule do): known only after the bytes have been streamed, so
+ * d_out and d_new_table may have been written by then.
+ * No live entry: n_entries = new_len = 0, an empty table is built, nothing
+ * else runs.
+ * On the context stream; synchronises (one wait behind the kernels, for the
+ * stream rule's outcome and n_crc_bad), like srd_batch_delete_hashed_device:
+ * the caller's writes to d_file and d_table must be complete, or ordered on
+ * that stream, before the call.  The workspace comes from the context
+ * (srd_ctx_device_bytes counts it). */
+typedef struct {
+  uint64_t n_entries;   /* entries written: the table's live keys whose indexed entry is not a tombstone */
+  uint64_t new_len;     /* length of the compacted store */
+  uint64_t kept_bytes;  /* sum of (payload length + 20) over them: estimate_compaction_savings' unique_entry_size */
+  uint64_t n_crc_bad;   /* written entries whose recomputed CRC-32 differs from the checksum stored in the source */
+  uint64_t first_bad;   /* source metadata offset of the first of them in output order; ~0 when there is none */
+} srd_compact_stats;
+int srd_compact_live_device(srd_ctx *ctx, const void *d_table, uint64_t table_bytes,
+                            const uint8_t *d_file, uint64_t file_len,
+                            uint8_t *d_out, uint64_t out_cap,
+                            void *d_new_table, uint64_t new_table_bytes,
+                            srd_compact_stats *stats);
 
 /* Synthetic store of the BASELINE configs written on the device (the
  * checksum-on-append writer of data_store.rs:847-939 for keys

@@ -18,7 +18,7 @@
 //     srd_table.h             the lookup table's rule: slot states, probe, claim, size arithmetic (the host entries
 //                             and a CPU check use it too)
 //     srd_index.hip           lookup table build and reads, iterator, compaction
-//     srd_index_live.hip      the table kept live: apply, export, batched delete
+//     srd_index_live.hip      the table kept live: apply, export, batched delete; the live compaction's two steps
 //     srd_probe.hip           stream probe
 //   host code (in include order: each file uses only the ones above it)
 //     srd_host.cpp / .h       no-HIP parsers (shard cuts, batch layout)
@@ -31,7 +31,7 @@
 //     srd_host_input.hip      staging, pinned host results, host-pointer entries
 //     srd_multi.hip           multi-GPU open
 //     srd_ops.hip             probe, batch digests, synth, writer, table / reads / maintenance, iterator,
-//                             compaction, payload gather, device append
+//                             compaction, payload gather, device append, live compaction
 //   this file               error / build-info entries, stamps read-outs, host self-test
 //
 // Glue scans/compactions use hipCUB (library primitives, like calling

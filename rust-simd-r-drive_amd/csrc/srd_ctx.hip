@@ -238,6 +238,7 @@ enum BufId {
   B_LV_XK, B_LV_XP, B_LV_FLAG, B_LV_POS, B_LV_ENT, B_LV_TOMB,        // export, batched delete
   B_GA_ST, B_GA_PLEN, B_GA_CHK, B_GA_OFF, B_GA_CPRE, B_GA_CNT, B_GA_UNIT, B_GA_RAW, B_GA_CRC,  // payload gather
   B_AP_END, B_AP_NZ,  // device append (on top of the gather's)
+  B_CL_XK, B_CL_XP, B_CL_LEN, B_CL_MO, B_CL_PACKED, B_CL_CNT,  // live compaction (on top of the export's, the iterator's and the append's)
   B_COUNT_
 };
 

@@ -1,6 +1,8 @@
 // srd_index_live.hip -- in-place maintenance of the device KeyIndexer table of
 // srd_index.hip: apply a batch of (key_hash, metadata offset, tombstone) pairs,
-// export the live pairs, lay out a batch of tombstones.
+// export the live pairs, lay out a batch of tombstones;
+// and the two steps srd_compact_live_device has around the append's path
+// (section 13).
 //
 // Reference being replaced (jzombie/rust-simd-r-drive v0.16.3-alpha):
 //   DataStore::reindex          src/storage_engine/data_store.rs:224-259
@@ -36,6 +38,11 @@ struct LiveArgs {
   uint64_t* op_val;     // [n]
   unsigned long long* cnt;  // [4] inserted, updated, removed (per distinct key), new slots needed
 };
+
+// KeyIndexer::pack(tag_from_hash(key_hash), offset) (key_indexer.rs:64-82)
+__device__ __forceinline__ uint64_t live_pack(uint64_t key_hash, uint64_t meta_off) {
+  return (key_hash >> 48 << 48) | (meta_off & 0xFFFFFFFFFFFFull);
+}
 
 // Latest-wins dedupe of the batch.  A scratch slot holds a batch position, so
 // its key is kh[position]: read from the input, never from a word another
@@ -86,7 +93,7 @@ __global__ void live_lookup_kernel(LiveArgs a) {
     if (a.dslot[ds] == (uint32_t)i + 1) {
       const uint64_t k = a.kh[i];
       const bool del = (a.dtomb[ds >> 5] >> (ds & 31)) & 1;
-      const uint64_t np = (k >> 48 << 48) | (a.mo[i] & 0xFFFFFFFFFFFFull);  // KeyIndexer::pack(tag_from_hash, offset)
+      const uint64_t np = live_pack(k, a.mo[i]);
       uint64_t s;
       const uint64_t p = table_find(a.t, k, &s);
       const bool found = p != TBL_EMPTY;
@@ -181,6 +188,42 @@ __global__ void live_tomb_entries_kernel(const uint64_t* q, const uint32_t* flag
                                          uint64_t tail, srd_write_entry* ent) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
     if (flag[i]) ent[pos[i]] = srd_write_entry{0, 1, q[i], tail + 21ull * pos[i], 0u, SRD_ENTRY_TOMB | SRD_ENTRY_HASHED};
+}
+
+// ---------------------------------------------------------------------------
+// srd_compact_live_device: the two steps around the
+// append's path.  The iterator's ranges [start, end) as the append's lengths --
+// its starts and key hashes are the append's src_off and key_hash arrays as
+// they are.
+__global__ __launch_bounds__(256) void compact_lens_kernel(const uint64_t* st, const uint64_t* en, uint64_t n,
+                                                           uint64_t* len) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) len[i] = en[i] - st[i];
+}
+
+// Behind the append's finish, per written entry: the recomputed CRC (the
+// gather kernels') against the checksum stored in the source, the
+// little-endian u32 at end + 16 (inside the file by entry_range) -- cnt[0]
+// counts the entries that differ, cnt[1] is the lowest output position among
+// them (preset to ~0) -- and the pair's value for the new table,
+// pack(key_hash >> 48, new metadata offset).
+__global__ __launch_bounds__(256) void compact_finish_kernel(const uint8_t* file, const uint64_t* en, const uint64_t* kh,
+                                                             const uint32_t* crc, const uint64_t* mo, uint64_t n,
+                                                             uint64_t* packed, unsigned long long* cnt) {
+  unsigned long long first = ~0ull;
+  // (whole waves in every round: the ballot sees 64 lanes)
+  const uint64_t rounds = (n + gridDim.x * 256ull - 1) / (gridDim.x * 256ull);
+  for (uint64_t r = 0; r < rounds; r++) {
+    const uint64_t i = (r * gridDim.x + blockIdx.x) * 256ull + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+      bad = crc[i] != ld_u32_unaligned(file, en[i] + 16);
+      packed[i] = live_pack(kh[i], mo[i]);
+      if (bad) first = min(first, (unsigned long long)i);
+    }
+    const uint64_t m = __ballot(bad);
+    if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(cnt, (unsigned long long)__builtin_popcountll(m));
+  }
+  if (first != ~0ull) atomicMin(cnt + 1, first);  // (a corrupt store only)
 }
 
 }  // namespace srd

@@ -1,7 +1,7 @@
 // srd_ops.hip -- host launch code of the remaining kernel families (included
 // by srd_api.hip): stream probe, batch digests, synth, batch writer, device
 // lookup table, batched reads and the table's maintenance, iterator and
-// compaction, payload gather, device append.
+// compaction, payload gather, device append, live compaction.
 
 // A device allocation / an event that lasts for one call, released on every return path
 // (no workspace buffer: as large as the caller's input, the context would keep and report it)
@@ -294,6 +294,16 @@ extern "C" int srd_batch_write(srd_ctx* c, uint64_t tail, const uint8_t* keys, c
 extern "C" uint64_t srd_index_table_bytes(uint64_t n) { return table_bytes_for(n); }
 static unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 8192)); }
 
+// the build enqueued on the context stream: every slot empty, then one claim per pair
+static int table_build_run(Ctx* c, const uint64_t* d_keys, const uint64_t* d_packed, uint64_t n, void* d_table,
+                           uint64_t table_bytes) {
+  const Table t = table_view(d_table, table_bytes);
+  HIPCHK(hipMemsetAsync(t.packed, 0xFF, (1ull << t.log2cap) * 8, c->stream));
+  if (n) idx_table_insert_kernel<<<grid_for(n), 256, 0, c->stream>>>(d_keys, d_packed, n, t);
+  LAUNCHED(c->stream, "idx_table_insert_kernel");
+  return 0;
+}
+
 extern "C" int srd_index_table_build_device(srd_ctx* c, const uint64_t* d_keys, const uint64_t* d_packed, uint64_t n,
                                             void* d_table, uint64_t table_bytes) {
   if (!c || !d_table || (n && (!d_keys || !d_packed)) || table_bytes < srd_index_table_bytes(n)) {
@@ -301,10 +311,7 @@ extern "C" int srd_index_table_build_device(srd_ctx* c, const uint64_t* d_keys, 
     return SRD_ERR_ARG;
   }
   HIPCHK(hipSetDevice(c->device));
-  const Table t = table_view(d_table, table_bytes);
-  HIPCHK(hipMemsetAsync(t.packed, 0xFF, (1ull << t.log2cap) * 8, c->stream));
-  if (n) idx_table_insert_kernel<<<grid_for(n), 256, 0, c->stream>>>(d_keys, d_packed, n, t);
-  LAUNCHED(c->stream, "idx_table_insert_kernel");
+  TRY(table_build_run(c, d_keys, d_packed, n, d_table, table_bytes));
   HIPCHK(spin_sync(c->stream));
   return 0;
 }
@@ -440,14 +447,12 @@ extern "C" int srd_index_table_apply_device(srd_ctx* c, void* d_table, uint64_t 
   return apply_impl(c, d_table, table_bytes, used, d_key_hashes, d_meta_offs, d_tomb, n, stats, stream_of(c, stream));
 }
 
-extern "C" int srd_index_table_export_device(srd_ctx* c, const void* d_table, uint64_t table_bytes,
-                                             uint64_t* d_keys_out, uint64_t* d_packed_out, uint64_t cap_out,
-                                             uint64_t* n_live) {
-  if (!c || !table_ok(d_table, table_bytes) || !n_live || (!d_keys_out != !d_packed_out)) {
-    set_err("bad argument");
-    return SRD_ERR_ARG;
-  }
-  HIPCHK(hipSetDevice(c->device));
+// The export enqueued on the context stream: the count (one wait), the gather
+// of the live pairs and their sort.  *keys_out / *packed_out are the caller's
+// arrays of cap_out elements (both null: the count only); with ws they are
+// context workspace sized by the count and handed back (srd_compact_live_device).
+static int export_run(Ctx* c, const void* d_table, uint64_t table_bytes, uint64_t** keys_out, uint64_t** packed_out,
+                      uint64_t cap_out, bool ws, uint64_t* n_live) {
   const Table t = table_view(d_table, table_bytes);
   const uint64_t cap = 1ull << t.log2cap;
   TRY(ensure(c, B_LV_CNT, 64));
@@ -458,7 +463,14 @@ extern "C" int srd_index_table_export_device(srd_ctx* c, const void* d_table, ui
   unsigned long long nl = 0;
   TRY(read_small(c, c->stream, {rd(cnt, &nl)}));
   *n_live = nl;
-  if (!d_keys_out || !nl) return 0;
+  if (!(ws || *keys_out) || !nl) return 0;
+  if (ws) {
+    TRY(ensure(c, B_CL_XK, nl * 8));
+    TRY(ensure(c, B_CL_XP, nl * 8));
+    *keys_out = P<uint64_t>(c, B_CL_XK);
+    *packed_out = P<uint64_t>(c, B_CL_XP);
+    cap_out = nl;
+  }
   if (nl > cap_out) { set_err("cap_out too small for the live pairs"); return SRD_ERR_ARG; }
   if (nl >= (1ull << 31)) { set_err("too many pairs"); return SRD_ERR_ARG; }
   // file order = ascending metadata offset: the offsets are distinct, so a
@@ -470,7 +482,19 @@ extern "C" int srd_index_table_export_device(srd_ctx* c, const void* d_table, ui
   live_gather_kernel<<<grid_for(cap), 256, 0, c->stream>>>(t.keys, t.packed, cap, cnt, P<uint64_t>(c, B_LV_XK),
                                                           P<uint64_t>(c, B_LV_XP), nl);
   LAUNCHED(c->stream, "live_gather_kernel");
-  TRY(sort_pairs48(c, P<uint64_t>(c, B_LV_XP), d_packed_out, P<uint64_t>(c, B_LV_XK), d_keys_out, nl));
+  TRY(sort_pairs48(c, P<uint64_t>(c, B_LV_XP), *packed_out, P<uint64_t>(c, B_LV_XK), *keys_out, nl));
+  return 0;
+}
+
+extern "C" int srd_index_table_export_device(srd_ctx* c, const void* d_table, uint64_t table_bytes,
+                                             uint64_t* d_keys_out, uint64_t* d_packed_out, uint64_t cap_out,
+                                             uint64_t* n_live) {
+  if (!c || !table_ok(d_table, table_bytes) || !n_live || (!d_keys_out != !d_packed_out)) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  TRY(export_run(c, d_table, table_bytes, &d_keys_out, &d_packed_out, cap_out, false, n_live));
   HIPCHK(spin_sync(c->stream));
   return 0;
 }
@@ -721,22 +745,20 @@ extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint
 // Payloads already in HBM appended to a store (srd_append.hip): layout, one
 // wait for the error word, the new tail and the unit counts, then the gather's
 // unit table, streaming kernel and combine with the store as their output,
-// and the finish enqueued on the stream
-extern "C" int srd_batch_append_device(srd_ctx* c, const uint8_t* d_payloads, uint64_t payloads_len,
-                                       const uint64_t* d_src_off, const uint64_t* d_len, const uint64_t* d_key_hashes,
-                                       uint64_t n, uint32_t flags, uint64_t tail, uint8_t* d_file, uint64_t file_cap,
-                                       uint64_t* new_tail, uint64_t* d_meta_off_out, void* stream) {
-  if (!c || !new_tail || (flags & ~SRD_APPEND_STREAM_RULE) || ((uintptr_t)d_file & 15) ||
-      (n && (!d_src_off || !d_len || !d_key_hashes || !d_file || !d_meta_off_out || (payloads_len && !d_payloads)))) {
-    set_err("bad argument");
-    return SRD_ERR_ARG;
-  }
-  *new_tail = tail;
-  if (n >= (1ull << 31)) { set_err("too many entries in one batch"); return SRD_ERR_ARG; }
-  if (!n) return 0;
-  const bool rule = flags & SRD_APPEND_STREAM_RULE;
-  HIPCHK(hipSetDevice(c->device));
-  hipStream_t s = stream_of(c, stream);
+// and the finish enqueued on the stream.  Two steps over device arrays, which
+// srd_batch_append_device and srd_compact_live_device both run: append_plan
+// decides (nothing of the store is written), append_commit enqueues the writes.
+struct AppendPlan {
+  AppendArgs a;  // (file and mo: append_commit's)
+  uint64_t new_tail, units, n_multi;
+};
+
+// The layout kernel, the two exclusive sums and the one wait; SRD_ERR_ARG with
+// the refusal's message for what the entries themselves decide (n < 2^31: the
+// caller's check; it fits hipCUB's int count)
+static int append_plan(Ctx* c, hipStream_t s, const uint8_t* d_payloads, uint64_t payloads_len,
+                       const uint64_t* d_src_off, const uint64_t* d_len, const uint64_t* d_key_hashes, uint64_t n,
+                       bool rule, uint64_t tail, AppendPlan* p) {
   TRY(ensure(c, B_GA_PLEN, n * 8));
   TRY(ensure(c, B_GA_CHK, n * 8));
   TRY(ensure(c, B_GA_OFF, n * 8));
@@ -746,7 +768,8 @@ extern "C" int srd_batch_append_device(srd_ctx* c, const uint8_t* d_payloads, ui
   TRY(ensure(c, B_AP_END, n * 8));
   if (rule) TRY(ensure(c, B_AP_NZ, n * 4));
   TRY(ensure_scan(c, (const uint64_t*)nullptr, (uint64_t*)nullptr, n));  // both scans below
-  AppendArgs a{};
+  AppendArgs& a = p->a;
+  a = AppendArgs{};
   a.pay = d_payloads;
   a.pay_len = payloads_len;
   a.src = d_src_off;
@@ -762,18 +785,16 @@ extern "C" int srd_batch_append_device(srd_ctx* c, const uint8_t* d_payloads, ui
   a.cnt = P<unsigned long long>(c, B_GA_CNT);
   a.crc = P<uint32_t>(c, B_GA_CRC);
   a.nz = rule ? P<uint32_t>(c, B_AP_NZ) : nullptr;
-  a.file = d_file;
-  a.mo = d_meta_off_out;
   HIPCHK(hipMemsetAsync(a.cnt, 0, 40, s));
   HIPCHK(hipMemsetAsync(a.cnt + 1, 0xFF, 8, s));  // the error word: none
   if (rule) HIPCHK(hipMemsetAsync(P<void>(c, B_AP_NZ), 0, n * 4, s));
   append_layout_kernel<<<grid_for(n), 256, 0, s>>>(a);
   LAUNCHED(s, "append_layout_kernel");
-  // everything the host decides on, on one wait (n < 2^31 fits hipCUB's int count)
-  uint64_t pre_last = 0, units = 0;
+  // everything the host decides on, on one wait
+  uint64_t pre_last = 0;
   struct { unsigned long long n_multi, err, coarse, len_last; } h{};
   TRY(scan_sum(c, (const uint64_t*)a.slot, P<uint64_t>(c, B_GA_OFF), n, s));
-  TRY(scan_sum_total(c, (const uint64_t*)a.chk, P<uint64_t>(c, B_GA_CPRE), n, s, &units, rd(a.pre + n - 1, &pre_last),
+  TRY(scan_sum_total(c, (const uint64_t*)a.chk, P<uint64_t>(c, B_GA_CPRE), n, s, &p->units, rd(a.pre + n - 1, &pre_last),
                      SmallRead{a.cnt, &h, sizeof h}));
   if (h.err != ~0ull) {
     const uint32_t st = append_err_status(h.err);
@@ -783,31 +804,34 @@ extern "C" int srd_batch_append_device(srd_ctx* c, const uint8_t* d_payloads, ui
                                      : "the batch would end at 2^48 or beyond (the index packs 48-bit offsets)");
     return SRD_ERR_ARG;
   }
-  uint64_t nt = 0;
-  if (!append_new_tail(tail, h.coarse, pre_last, h.len_last, &nt)) {
+  if (!append_new_tail(tail, h.coarse, pre_last, h.len_last, &p->new_tail)) {
     set_err("the batch would end at 2^48 or beyond (the index packs 48-bit offsets)");
     return SRD_ERR_ARG;
   }
-  if (srd_padded_size(nt) > file_cap) {
-    set_err("file_cap too small for the batch: it ends at " + std::to_string(nt));
-    return SRD_ERR_ARG;
-  }
-  {  // the blob may not lie in what the call writes
-    const uintptr_t p0 = (uintptr_t)d_payloads, p1 = p0 + payloads_len;
-    const uintptr_t w0 = (uintptr_t)d_file + tail, w1 = (uintptr_t)d_file + gather_pad64(nt);
-    if (payloads_len && p0 < w1 && w0 < p1) { set_err("d_payloads overlaps the bytes the batch writes"); return SRD_ERR_ARG; }
-  }
+  p->n_multi = h.n_multi;
+  return 0;
+}
+
+// The planned batch written to d_file (file byte j at d_file[j]) and its
+// metadata offsets to d_mo, enqueued on s; the one refusal left (too many
+// units) comes before anything is written.  Under the rule the outcome is in
+// a.cnt[4] once the stream has run: the caller's wait (append_null_only).
+static int append_commit(Ctx* c, hipStream_t s, AppendPlan* p, uint8_t* d_file, uint64_t* d_mo) {
+  AppendArgs& a = p->a;
+  a.file = d_file;
+  a.mo = d_mo;
+  const uint64_t units = p->units;
   if (units >= (1ull << 32)) { set_err("too many work units in one batch"); return SRD_ERR_ARG; }
   TRY(ensure(c, B_GA_UNIT, units * 4));
   TRY(ensure(c, B_GA_RAW, units * 4));
   // the gather's kernels: the blob is their file, the store from base on their
   // output, the layout's prefix their output offsets (64-aligned: base + pre)
   PayloadGatherArgs ga{};
-  ga.file = d_payloads;
-  ga.flen = payloads_len;
-  ga.start = d_src_off;
+  ga.file = a.pay;
+  ga.flen = a.pay_len;
+  ga.start = a.src;
   ga.end = a.end;
-  ga.n = n;
+  ga.n = a.n;
   ga.chk = a.chk;
   ga.off = P<uint64_t>(c, B_GA_OFF);
   ga.cpre = P<uint64_t>(c, B_GA_CPRE);
@@ -820,21 +844,150 @@ extern "C" int srd_batch_append_device(srd_ctx* c, const uint8_t* d_payloads, ui
   payload_units_kernel<<<grid_for(units), 256, 0, s>>>(ga);
   LAUNCHED(s, "payload_units_kernel");
   const unsigned g = (unsigned)std::min<uint64_t>((units + SCAN_WAVES_V2 - 1) / SCAN_WAVES_V2, c->scan_blocks);
-  if (rule) payload_gather_kernel<true><<<g, SCAN_WAVES_V2 * 64, 0, s>>>(ga);
+  if (a.nz) payload_gather_kernel<true><<<g, SCAN_WAVES_V2 * 64, 0, s>>>(ga);
   else payload_gather_kernel<<<g, SCAN_WAVES_V2 * 64, 0, s>>>(ga);
   LAUNCHED(s, "payload_gather_kernel");
-  if (h.n_multi) payload_combine_kernel<<<(unsigned)std::min<uint64_t>((n + 3) / 4, 4096), 256, 0, s>>>(ga);
+  if (p->n_multi) payload_combine_kernel<<<(unsigned)std::min<uint64_t>((a.n + 3) / 4, 4096), 256, 0, s>>>(ga);
   LAUNCHED(s, "payload_combine_kernel");
-  append_finish_kernel<<<(unsigned)std::min<uint64_t>((n + 255) / 256, 4096), 256, 0, s>>>(a);
+  append_finish_kernel<<<(unsigned)std::min<uint64_t>((a.n + 255) / 256, 4096), 256, 0, s>>>(a);
   LAUNCHED(s, "append_finish_kernel");
-  if (rule) {  // write_stream's check comes after the bytes (data_store.rs:783-797): the second wait
+  return 0;
+}
+
+// write_stream's check comes after the bytes (data_store.rs:783-797)
+static int append_null_only(unsigned long long null_only) {
+  if (!null_only) return 0;
+  set_err("NULL-byte-only streams cannot be written directly.");
+  return SRD_ERR_ARG;
+}
+
+extern "C" int srd_batch_append_device(srd_ctx* c, const uint8_t* d_payloads, uint64_t payloads_len,
+                                       const uint64_t* d_src_off, const uint64_t* d_len, const uint64_t* d_key_hashes,
+                                       uint64_t n, uint32_t flags, uint64_t tail, uint8_t* d_file, uint64_t file_cap,
+                                       uint64_t* new_tail, uint64_t* d_meta_off_out, void* stream) {
+  if (!c || !new_tail || (flags & ~SRD_APPEND_STREAM_RULE) || ((uintptr_t)d_file & 15) ||
+      (n && (!d_src_off || !d_len || !d_key_hashes || !d_file || !d_meta_off_out || (payloads_len && !d_payloads)))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  *new_tail = tail;
+  if (n >= (1ull << 31)) { set_err("too many entries in one batch"); return SRD_ERR_ARG; }
+  if (!n) return 0;
+  const bool rule = flags & SRD_APPEND_STREAM_RULE;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream_of(c, stream);
+  AppendPlan p{};
+  TRY(append_plan(c, s, d_payloads, payloads_len, d_src_off, d_len, d_key_hashes, n, rule, tail, &p));
+  const uint64_t nt = p.new_tail;
+  if (srd_padded_size(nt) > file_cap) {
+    set_err("file_cap too small for the batch: it ends at " + std::to_string(nt));
+    return SRD_ERR_ARG;
+  }
+  {  // the blob may not lie in what the call writes
+    const uintptr_t p0 = (uintptr_t)d_payloads, p1 = p0 + payloads_len;
+    const uintptr_t w0 = (uintptr_t)d_file + tail, w1 = (uintptr_t)d_file + gather_pad64(nt);
+    if (payloads_len && p0 < w1 && w0 < p1) { set_err("d_payloads overlaps the bytes the batch writes"); return SRD_ERR_ARG; }
+  }
+  TRY(append_commit(c, s, &p, d_file, d_meta_off_out));
+  if (rule) {  // the second wait
     unsigned long long null_only = 0;
-    TRY(read_small(c, s, {rd(a.cnt + 4, &null_only)}));
-    if (null_only) {
-      set_err("NULL-byte-only streams cannot be written directly.");
+    TRY(read_small(c, s, {rd(p.a.cnt + 4, &null_only)}));
+    TRY(append_null_only(null_only));
+  }
+  *new_tail = nt;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// A live session compacted (srd_index_live.hip's compact_* kernels around the
+// append's path): the export's body and the iterator's
+// into workspace, the append's plan (the new length), the refusals, then the
+// append's commit, the CRC comparison with the pairs for the new table, the
+// table build, and one wait for the outcome
+static bool ranges_meet(const void* a, uint64_t an, const void* b, uint64_t bn) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a && b && an && bn && a0 < b0 + bn && b0 < a0 + an;
+}
+
+extern "C" int srd_compact_live_device(srd_ctx* c, const void* d_table, uint64_t table_bytes, const uint8_t* d_file,
+                                       uint64_t file_len, uint8_t* d_out, uint64_t out_cap, void* d_new_table,
+                                       uint64_t new_table_bytes, srd_compact_stats* stats) {
+  if (stats) *stats = srd_compact_stats{0, 0, 0, 0, ~0ull};
+  if (!c || !stats || !table_ok(d_table, table_bytes) || (file_len && !d_file) || (d_out && !d_new_table)) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  if (d_out) {  // what the arguments decide on their own, before anything runs
+    if ((uintptr_t)d_out & 15) { set_err("d_out is not 16-byte aligned"); return SRD_ERR_ARG; }
+    const uint64_t padded = srd_padded_size(file_len);
+    if (ranges_meet(d_out, out_cap, d_file, padded) || ranges_meet(d_out, out_cap, d_table, table_bytes)) {
+      set_err("d_out overlaps the store or its table");
+      return SRD_ERR_ARG;
+    }
+    if (ranges_meet(d_new_table, new_table_bytes, d_file, padded) ||
+        ranges_meet(d_new_table, new_table_bytes, d_table, table_bytes) ||
+        ranges_meet(d_new_table, new_table_bytes, d_out, out_cap)) {
+      set_err("d_new_table overlaps the store, its table or d_out");
       return SRD_ERR_ARG;
     }
   }
-  *new_tail = nt;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  // the live pairs in file order, then par_iter_entries' filter, newest first
+  uint64_t nl = 0, nv = 0, kept = 0;
+  uint64_t *xk = nullptr, *xp = nullptr;
+  TRY(export_run(c, d_table, table_bytes, &xk, &xp, 0, true, &nl));
+  if (nl) {
+    TRY(ensure(c, B_IT_OST, nl * 8));
+    TRY(ensure(c, B_IT_OEN, nl * 8));
+    TRY(ensure(c, B_IT_OKH, nl * 8));
+    TRY(iter_run(c, d_file, file_len, xp, nl, P<uint64_t>(c, B_IT_OST), P<uint64_t>(c, B_IT_OEN), nullptr,
+                 P<uint64_t>(c, B_IT_OKH), &nv, &kept));
+  }
+  stats->n_entries = nv;
+  stats->kept_bytes = kept;
+  AppendPlan p{};
+  const uint64_t* st = P<uint64_t>(c, B_IT_OST);
+  const uint64_t* en = P<uint64_t>(c, B_IT_OEN);
+  const uint64_t* kh = P<uint64_t>(c, B_IT_OKH);
+  if (nv) {  // (nv <= nl < 2^31: the append's bound on n holds)
+    TRY(ensure(c, B_CL_LEN, nv * 8));
+    compact_lens_kernel<<<grid_for(nv), 256, 0, s>>>(st, en, nv, P<uint64_t>(c, B_CL_LEN));
+    LAUNCHED(s, "compact_lens_kernel");
+    TRY(append_plan(c, s, d_file, file_len, st, P<uint64_t>(c, B_CL_LEN), kh, nv, true, 0, &p));
+    stats->new_len = p.new_tail;
+  }
+  if (!d_out) return 0;  // the planning call
+  if (nv && srd_padded_size(stats->new_len) > out_cap) {
+    set_err("out_cap too small for the compacted store: it ends at " + std::to_string(stats->new_len));
+    return SRD_ERR_ARG;
+  }
+  if (new_table_bytes < srd_index_table_bytes(nv)) {
+    set_err("new_table_bytes < srd_index_table_bytes(n_entries)");
+    return SRD_ERR_ARG;
+  }
+  if (!nv) {  // no live entry: the empty table
+    TRY(table_build_run(c, nullptr, nullptr, 0, d_new_table, new_table_bytes));
+    HIPCHK(spin_sync(s));
+    return 0;
+  }
+  TRY(ensure(c, B_CL_MO, nv * 8));
+  TRY(ensure(c, B_CL_PACKED, nv * 8));
+  TRY(ensure(c, B_CL_CNT, 64));
+  unsigned long long* cnt = P<unsigned long long>(c, B_CL_CNT);
+  TRY(append_commit(c, s, &p, d_out, P<uint64_t>(c, B_CL_MO)));
+  HIPCHK(hipMemsetAsync(cnt, 0, 8, s));
+  HIPCHK(hipMemsetAsync(cnt + 1, 0xFF, 8, s));  // the first bad position: none
+  compact_finish_kernel<<<grid_for(nv), 256, 0, s>>>(d_file, en, kh, p.a.crc, P<uint64_t>(c, B_CL_MO), nv,
+                                                     P<uint64_t>(c, B_CL_PACKED), cnt);
+  LAUNCHED(s, "compact_finish_kernel");
+  TRY(table_build_run(c, kh, P<uint64_t>(c, B_CL_PACKED), nv, d_new_table, new_table_bytes));
+  // the one wait behind the kernels: the stream rule's outcome and the CRC comparison's
+  unsigned long long null_only = 0;
+  struct { unsigned long long n_bad, first; } h{};
+  TRY(read_small(c, s, {rd(p.a.cnt + 4, &null_only), SmallRead{cnt, &h, sizeof h}}));
+  TRY(append_null_only(null_only));
+  stats->n_crc_bad = h.n_bad;
+  if (h.n_bad) TRY(read_small(c, s, {rd(en + h.first, &stats->first_bad)}));  // (a corrupt store only) its source metadata offset
   return 0;
 }

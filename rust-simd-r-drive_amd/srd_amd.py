@@ -71,7 +71,7 @@ EXPORTS = [
     "srd_validate_index_multi_device", "srd_ctx_multi_summary", "srd_ctx_scan_list", "srd_ctx_set_timing_every",
     "srd_stream_probe_device", "srd_ctx_multi_shard_ms",
     "srd_index_table_apply_device", "srd_index_table_export_device", "srd_batch_delete_hashed_device",
-    "srd_payload_gather_device", "srd_batch_append_device",
+    "srd_payload_gather_device", "srd_batch_append_device", "srd_compact_live_device",
 ]
 
 
@@ -111,6 +111,15 @@ class ApplyStats(C.Structure):
 
     def as_tuple(self):
         return int(self.n_inserted), int(self.n_updated), int(self.n_removed)
+
+
+class CompactStats(C.Structure):
+    """srd_compact_stats (include/srd_amd.h)"""
+    _fields_ = [("n_entries", C.c_uint64), ("new_len", C.c_uint64), ("kept_bytes", C.c_uint64),
+                ("n_crc_bad", C.c_uint64), ("first_bad", C.c_uint64)]
+
+    def __repr__(self):
+        return "CompactStats(" + ", ".join(f"{n}={int(getattr(self, n))}" for n, _ in self._fields_) + ")"
 
 
 def build_info() -> str:
@@ -202,6 +211,7 @@ def lib():
         L.srd_payload_gather_device.argtypes = [vp, vp, u64, vp, vp, u64, u32, vp, u64, vp, vp, vp,
                                                 C.POINTER(u64), vp]
         L.srd_batch_append_device.argtypes = [vp, vp, u64, vp, vp, vp, u64, u32, u64, vp, u64, C.POINTER(u64), vp, vp]
+        L.srd_compact_live_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(CompactStats)]
         L.srd_iter_entries_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
         L.srd_estimate_compaction_savings_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.srd_compact_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, vp]
@@ -1208,6 +1218,24 @@ def compact_device(d_file: int, file_len: int, d_index_packed: int, n_index: int
     return out[: int(nl.value)]
 
 
+def compact_live_device(d_table: int, table_bytes: int, d_file: int, file_len: int, d_out: int | None = None,
+                        out_cap: int = 0, d_new_table: int | None = None, new_table_bytes: int = 0,
+                        ctx: Context | None = None) -> CompactStats:
+    """srd_compact_live_device as it is (device pointers in, the stats out): on
+    the context stream, synchronises.  d_out None is the planning call.  SrdError
+    carries the refusal's message, `.rc` and `.stats` (what was known by then)."""
+    ctx = ctx or default_ctx()
+    st = CompactStats()
+    rc = lib().srd_compact_live_device(ctx.h, C.c_void_p(d_table), table_bytes, C.c_void_p(d_file), file_len,
+                                       C.c_void_p(d_out), out_cap, C.c_void_p(d_new_table), new_table_bytes,
+                                       C.byref(st))
+    if rc != 0:
+        e = SrdError(f"srd error {rc}: {lib().srd_last_error().decode()}")
+        e.rc, e.stats = rc, st
+        raise e
+    return st
+
+
 # ---------------------------------------------------------------------------
 # A store resident in HBM with its index kept live: write -> reindex -> read
 # (DataStoreWriter / DataStoreReader of data_store.rs over one device buffer)
@@ -1530,6 +1558,79 @@ class DeviceStore:
         """Every live payload in EntryIterator order (newest first), gathered and
         verified: the index's export, srd_iter_entries_device, then the gather of
         its ranges."""
-        _k, p = self.index.export()  # synchronises
-        st, en, _mo, _kh = _iter_entries(self.buf.data_ptr(), self._tail, p.data_ptr(), p.numel(), self.ctx)
+        st, en, _mo, _kh = self._live_entries()
         return gather_ranges(self.buf.data_ptr(), self._tail, st, en, 0, self.ctx)
+
+    def _live_entries(self):
+        """The live index's export, then srd_iter_entries_device over it: device
+        int64 tensors (start, end, meta_off, key_hash), newest first."""
+        _k, p = self.index.export()  # synchronises
+        return _iter_entries(self.buf.data_ptr(), self._tail, p.data_ptr(), p.numel(), self.ctx)
+
+    def iter_entries(self):
+        """iter_entries (data_store.rs:276-280) over the live index: numpy arrays
+        (start, end, meta_off, key_hash), newest first (EntryIterator order)."""
+        return tuple(t.cpu().numpy().view(np.uint64) for t in self._live_entries())
+
+    # -- compaction and growth --------------------------------------------------------------
+
+    def _compact_plan(self) -> CompactStats:
+        idx = self.index
+        idx._lib_after_torch()
+        return compact_live_device(idx.table.data_ptr(), idx.nbytes, self.buf.data_ptr(), self._tail, ctx=self.ctx)
+
+    def estimate_compaction_savings(self) -> int:
+        """estimate_compaction_savings (data_store.rs:605-616): the tail less the
+        bytes the live entries need (payload + 20 each), saturating at 0."""
+        return max(self._tail - int(self._compact_plan().kept_bytes), 0)
+
+    def compact(self, capacity: int | None = None, allow_bad_crc: bool = False) -> CompactStats:
+        """DataStore::compact (data_store.rs:706-749) of the session, on the device
+        (srd_compact_live_device): every live entry, newest first, re-written from
+        offset 0 into a new buffer of padded_size(capacity) bytes (default: the
+        current buffer's size) with its checksum recomputed, and the index rebuilt
+        for the new offsets; then buffer, tail and index table are replaced in one
+        step.  Both buffers -- and both tables -- are held in HBM during the call.
+        A key whose indexed entry is a tombstone on disk (such keys can only come
+        from `open`) disappears from len(), as it would on re-opening the compacted
+        file in the reference.  ValueError when the compacted store does not fit the
+        capacity, and -- unless allow_bad_crc -- when a live payload's recomputed
+        CRC differs from its stored checksum (the message names n_crc_bad and
+        first_bad, the first such entry's metadata offset in the old store; the
+        reference would silently give it a fresh, matching checksum); SrdError for
+        the library's refusals (a live payload of NULL bytes only).  Any error
+        leaves the session exactly as it was: same buffer, tail and table."""
+        import torch
+        idx = self.index
+        plan = self._compact_plan()
+        nbytes = padded_size(capacity) if capacity is not None else self.buf.numel()
+        if padded_size(int(plan.new_len)) > nbytes:
+            raise ValueError(f"the compacted store ends at {int(plan.new_len)}: beyond the capacity")
+        dev = self.buf.device
+        buf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        tbytes = int(lib().srd_index_table_bytes(max(int(plan.n_entries), 1)))
+        table = torch.empty(tbytes, dtype=torch.uint8, device=dev)
+        idx._lib_after_torch()  # (behind torch's zero fill)
+        st = compact_live_device(idx.table.data_ptr(), idx.nbytes, self.buf.data_ptr(), self._tail, buf.data_ptr(),
+                                 nbytes, table.data_ptr(), tbytes, self.ctx)  # synchronises
+        if st.n_crc_bad and not allow_bad_crc:
+            raise ValueError(f"live payloads fail their stored checksum: n_crc_bad = {int(st.n_crc_bad)}, first_bad = "
+                             f"{int(st.first_bad)} (its metadata offset); compact(allow_bad_crc=True) keeps them")
+        n = int(st.n_entries)
+        self.buf, self._tail = buf, int(st.new_len)
+        idx.table, idx.nbytes, idx.n, idx._used, idx._live = table, tbytes, n, n, n
+        return st
+
+    def reserve(self, capacity: int) -> None:
+        """A buffer that can grow to `capacity` bytes: a new zeroed tensor, the
+        bytes [0, padded_size(tail)) copied on the device, then the swap.  For when
+        the live data itself has outgrown the buffer (dead space: `compact`).
+        ValueError when capacity is below the tail."""
+        import torch
+        if capacity < self._tail:
+            raise ValueError(f"capacity {capacity} is below the tail {self._tail}")
+        buf = torch.zeros(padded_size(capacity), dtype=torch.uint8, device=self.buf.device)
+        n = min(padded_size(self._tail), self.buf.numel(), buf.numel())
+        self.index._sync_lib()  # what the library wrote has landed before torch reads it
+        buf[:n].copy_(self.buf[:n])
+        self.buf = buf
