@@ -698,6 +698,71 @@ int srd_batch_append_device(srd_ctx *ctx, const uint8_t *d_payloads, uint64_t pa
                             uint64_t *new_tail, uint64_t *d_meta_off_out /* n */,
                             void *stream);
 
+/* ---- entries whose payload is a sequence of device segments ----
+ *   srd_batch_append_segments_device <- n write_stream_with_key_hash calls
+ *                              (data_store.rs:758-825): the payload arrives in
+ *                              pieces, the checksum runs over the pieces in
+ *                              order (:775,788), the entry is laid out like
+ *                              any other
+ * src_ptrs / src_lens are HOST arrays of n_src device ranges [src_ptrs[k],
+ * src_ptrs[k] + src_lens[k]): the call's source table.  The sources are only
+ * read; they may overlap each other and may be the store itself below tail.
+ * d_segs (device) holds n_segs segments, each the bytes sources[src][off ..
+ * off + len); one segment may name the same bytes as another, len may be 0.
+ * d_seg_first (device, n + 1 values, first[0] = 0, non-decreasing, first[n] =
+ * n_segs): entry i's payload is the concatenation of the segments d_segs[
+ * first[i] .. first[i + 1]) in order, its length len_i the sum of theirs.
+ * Everything else is srd_batch_append_device's contract: d_file[j] = file byte
+ * j, writable to file_cap bytes, 16-byte aligned; with P_0 = roundup64(tail)
+ * entry i's payload lies at P_i, its metadata {key_hash, prev_offset,
+ * crc32(payload)} at m_i = P_i + len_i, prev_offset_0 = tail, prev_offset_i =
+ * m_(i-1) + 20, P_(i+1) = roundup64(m_i + 20), *new_tail = m_(n-1) + 20; the
+ * bytes [tail, P_0) and [m_i + 20, P_(i+1)) are zero; d_meta_off_out[i] = m_i;
+ * the call touches no index table.  No byte below tail changes, none at or
+ * above roundup64(*new_tail) is touched, and [*new_tail, roundup64(*new_tail))
+ * is left alone or written as zero.  Whole 16-byte vectors of the store are
+ * written at any source and destination alignment (a piece's destination is
+ * wherever the previous piece ended).  n == 0: *new_tail = tail, nothing runs.
+ * SRD_ERR_ARG, nothing written to d_file or d_meta_off_out, *new_tail = tail
+ * (the first refused entry in batch order decides the message):
+ *   an entry with no segments, or only zero-length ones ("Payload cannot be
+ *     empty.", data_store.rs:799-804);
+ *   a malformed segment -- src >= n_src, reserved != 0, a range not inside its
+ *     source (judged without wrap), an entry length of 2^48 or more: such a
+ *     segment is never dereferenced, the message names the entry, and the
+ *     entry is refused for it whatever its total length;
+ *   a malformed d_seg_first: first[0] != 0, a decreasing pair, first[n] !=
+ *     n_segs;
+ *   a new tail of 2^48 or more; srd_padded_size(new tail) > file_cap (the
+ *     message names file_cap); n >= 2^31; n_segs >= 2^31; 2^32 or more work
+ *     units (pieces of at most SRD_GATHER_CHUNK bytes of one segment);
+ *     flags != 0;
+ *   a source [src_ptrs[k], src_ptrs[k] + src_lens[k]) that meets d_file[tail ..
+ *     roundup64(new tail)).
+ * The stream rule is always on -- this is write_stream: a payload whose bytes
+ * are all 0 (any length, over all its segments) fails the call with
+ * "NULL-byte-only streams cannot be written directly." (:792-797), known only
+ * after the bytes have been streamed, as documented for
+ * SRD_APPEND_STREAM_RULE: bytes at or above tail and d_meta_off_out may have
+ * been written, *new_tail = tail, the caller's tail and index do not move.
+ * Ordered on `stream`; the call waits twice: once for the error word, the new
+ * tail and the unit counts, and once more, for the kernels, before it returns
+ * (later work on `stream` sees the store and d_meta_off_out).  The workspace
+ * comes from the context (srd_ctx_device_bytes counts it). */
+typedef struct {
+  uint32_t src;       /* index into the call's source table */
+  uint32_t reserved;  /* 0 */
+  uint64_t off, len;  /* the bytes sources[src][off .. off + len); len may be 0 */
+} srd_segment;        /* 24 bytes, no padding */
+int srd_batch_append_segments_device(srd_ctx *ctx, const uint8_t *const *src_ptrs,
+                                     const uint64_t *src_lens, uint64_t n_src,
+                                     const srd_segment *d_segs, uint64_t n_segs,
+                                     const uint64_t *d_seg_first /* n + 1 */,
+                                     const uint64_t *d_key_hashes, uint64_t n, uint32_t flags /* 0 */,
+                                     uint64_t tail, uint8_t *d_file, uint64_t file_cap,
+                                     uint64_t *new_tail, uint64_t *d_meta_off_out /* n */,
+                                     void *stream);
+
 /* ---- a live session compacted on the device, its index carried over ----
  *   srd_compact_live_device <- DataStore::compact (data_store.rs:706-749) over
  *                              iter_entries (:276-280) / EntryIterator

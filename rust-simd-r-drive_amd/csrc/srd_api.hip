@@ -15,6 +15,9 @@
 //     srd_gather.hip          verified payloads: batched gather with checksum check (uses the writer's helpers)
 //     srd_append.h            the device append's range rule, layout and refusals (a CPU check uses it too)
 //     srd_append.hip          payloads in HBM appended to a store: layout and finish around the gather's kernels
+//     srd_segments.h          the segment append's table rule, unit cut, unit descriptor and CRC combine (a CPU check uses it too)
+//     srd_segments.hip        entries made of device segments appended to a store: layout, units, the streaming
+//                             kernel for any source / destination alignment, combine (around the append's finish)
 //     srd_table.h             the lookup table's rule: slot states, probe, claim, size arithmetic (the host entries
 //                             and a CPU check use it too)
 //     srd_index.hip           lookup table build and reads, iterator, compaction
@@ -31,7 +34,7 @@
 //     srd_host_input.hip      staging, pinned host results, host-pointer entries
 //     srd_multi.hip           multi-GPU open
 //     srd_ops.hip             probe, batch digests, synth, writer, table / reads / maintenance, iterator,
-//                             compaction, payload gather, device append, live compaction
+//                             compaction, payload gather, device append, segment append, live compaction
 //   this file               error / build-info entries, stamps read-outs, host self-test
 //
 // Glue scans/compactions use hipCUB (library primitives, like calling
@@ -63,6 +66,8 @@
 #include "srd_gather.hip"
 #include "srd_append.h"
 #include "srd_append.hip"
+#include "srd_segments.h"
+#include "srd_segments.hip"
 #include "srd_table.h"
 #include "srd_index.hip"
 #include "srd_index_live.hip"

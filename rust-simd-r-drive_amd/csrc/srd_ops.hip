@@ -1,7 +1,7 @@
 // srd_ops.hip -- host launch code of the remaining kernel families (included
 // by srd_api.hip): stream probe, batch digests, synth, batch writer, device
 // lookup table, batched reads and the table's maintenance, iterator and
-// compaction, payload gather, device append, live compaction.
+// compaction, payload gather, device append, segment append, live compaction.
 
 // A device allocation / an event that lasts for one call, released on every return path
 // (no workspace buffer: as large as the caller's input, the context would keep and report it)
@@ -894,6 +894,177 @@ extern "C" int srd_batch_append_device(srd_ctx* c, const uint8_t* d_payloads, ui
     TRY(read_small(c, s, {rd(p.a.cnt + 4, &null_only)}));
     TRY(append_null_only(null_only));
   }
+  *new_tail = nt;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Entries made of device segments appended to a store (srd_segments.hip): the
+// append's two steps with a payload that arrives in pieces.  segments_plan
+// uploads the source table, runs the layout kernel and the two exclusive sums
+// (the entries' slots, the segments' unit counts) and waits once for the error
+// word, the new tail and the unit counts; segments_commit enqueues the unit
+// descriptors, the streaming kernel, the combine and the append's finish.
+struct SegmentsPlan {
+  SegArgs a;
+  uint64_t new_tail, units, n_multi;
+};
+
+static int segments_plan(Ctx* c, hipStream_t s, const std::vector<uint64_t>& srcs, const srd_segment* d_segs,
+                         uint64_t n_segs, const uint64_t* d_seg_first, uint64_t n, uint64_t tail, SegmentsPlan* p) {
+  const uint64_t n_src = srcs.size() / 2;
+  TRY(ensure(c, B_GA_PLEN, n * 8));
+  TRY(ensure(c, B_GA_CHK, n * 8));
+  TRY(ensure(c, B_GA_OFF, n * 8));
+  TRY(ensure(c, B_GA_CRC, n * 4));
+  TRY(ensure(c, B_GA_CNT, 64));
+  TRY(ensure(c, B_AP_NZ, n * 4));
+  TRY(ensure(c, B_SG_SRC, srcs.size() * 8));
+  TRY(ensure(c, B_SG_LEN, n * 8));
+  TRY(ensure(c, B_SG_OFF, n_segs * 8));
+  TRY(ensure(c, B_SG_UN, n_segs * 8));
+  TRY(ensure(c, B_SG_UPRE, n_segs * 8));
+  TRY(ensure(c, B_SG_ENT, n_segs * 4));
+  TRY(ensure_scan(c, (const uint64_t*)nullptr, (uint64_t*)nullptr, std::max(n, n_segs)));  // both scans below
+  SegArgs& a = p->a;
+  a = SegArgs{};
+  a.srcs = P<uint64_t>(c, B_SG_SRC);
+  a.n_src = n_src;
+  a.segs = d_segs;
+  a.n_segs = n_segs;
+  a.first = d_seg_first;
+  a.n = n;
+  a.base = append_base(tail);
+  a.len = P<uint64_t>(c, B_SG_LEN);
+  a.slot = P<uint64_t>(c, B_GA_PLEN);
+  a.eun = P<uint64_t>(c, B_GA_CHK);
+  a.pre = P<uint64_t>(c, B_GA_OFF);
+  a.soff = P<uint64_t>(c, B_SG_OFF);
+  a.sun = P<uint64_t>(c, B_SG_UN);
+  a.upre = P<uint64_t>(c, B_SG_UPRE);
+  a.sent = P<uint32_t>(c, B_SG_ENT);
+  a.cnt = P<unsigned long long>(c, B_GA_CNT);
+  a.crc = P<uint32_t>(c, B_GA_CRC);
+  a.nz = P<uint32_t>(c, B_AP_NZ);
+  // (the table is the caller's for the call: the wait below comes before the return)
+  if (n_src) HIPCHK(hipMemcpyAsync(P<void>(c, B_SG_SRC), srcs.data(), srcs.size() * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(a.cnt, 0, 40, s));
+  HIPCHK(hipMemsetAsync(a.cnt + 1, 0xFF, 8, s));  // the error word: none
+  HIPCHK(hipMemsetAsync(a.nz, 0, n * 4, s));
+  if (n_segs) HIPCHK(hipMemsetAsync(a.sun, 0, n_segs * 8, s));  // (a refused entry leaves its segments' counts alone)
+  segments_layout_kernel<<<grid_for(n), 256, 0, s>>>(a);
+  LAUNCHED(s, "segments_layout_kernel");
+  // everything the host decides on, on one wait
+  uint64_t pre_last = 0;
+  struct { unsigned long long n_multi, err, coarse, len_last; } h{};
+  p->units = 0;
+  if (n_segs) {
+    TRY(scan_sum(c, (const uint64_t*)a.slot, P<uint64_t>(c, B_GA_OFF), n, s));
+    TRY(scan_sum_total(c, (const uint64_t*)a.sun, P<uint64_t>(c, B_SG_UPRE), n_segs, s, &p->units,
+                       rd(a.pre + n - 1, &pre_last), SmallRead{a.cnt, &h, sizeof h}));
+  } else {
+    TRY(read_small(c, s, {SmallRead{a.cnt, &h, sizeof h}}));  // (every entry is empty: refused below)
+  }
+  if (h.err != ~0ull) {
+    const uint32_t st = append_err_status(h.err);
+    const std::string i = std::to_string(h.err >> 8);
+    set_err(st == APPEND_EMPTY      ? "Payload cannot be empty."
+            : st == SEG_BAD_SEGMENT ? "entry " + i + " has a malformed segment (src, reserved, or a range outside its source)"
+            : st == SEG_BAD_FIRST   ? "d_seg_first is malformed at entry " + i
+                                    : "entry " + i + " is 2^48 bytes or longer (the index packs 48-bit offsets)");
+    return SRD_ERR_ARG;
+  }
+  if (!append_new_tail(tail, h.coarse, pre_last, h.len_last, &p->new_tail)) {
+    set_err("the batch would end at 2^48 or beyond (the index packs 48-bit offsets)");
+    return SRD_ERR_ARG;
+  }
+  p->n_multi = h.n_multi;
+  return 0;
+}
+
+static int segments_commit(Ctx* c, hipStream_t s, SegmentsPlan* p, const uint64_t* d_key_hashes, uint64_t tail,
+                           uint8_t* d_file, uint64_t* d_mo) {
+  SegArgs& a = p->a;
+  const uint64_t units = p->units;
+  if (units >= (1ull << 32)) { set_err("too many work units in one batch"); return SRD_ERR_ARG; }
+  TRY(ensure(c, B_SG_UNIT, units * sizeof(SegUnit)));
+  TRY(ensure(c, B_GA_RAW, units * 4));
+  a.unit = P<SegUnit>(c, B_SG_UNIT);
+  a.n_units = units;
+  a.raw = P<uint32_t>(c, B_GA_RAW);
+  a.file = d_file;
+  segments_units_kernel<<<grid_for(units), 256, 0, s>>>(a);
+  LAUNCHED(s, "segments_units_kernel");
+  const unsigned g = (unsigned)std::min<uint64_t>((units + SCAN_WAVES_V2 - 1) / SCAN_WAVES_V2, c->scan_blocks);
+  segments_stream_kernel<<<g, SCAN_WAVES_V2 * 64, 0, s>>>(a);
+  LAUNCHED(s, "segments_stream_kernel");
+  if (p->n_multi) {
+    segments_terms_kernel<<<grid_for(units), 256, 0, s>>>(a);
+    LAUNCHED(s, "segments_terms_kernel");
+    segments_combine_kernel<<<(unsigned)std::min<uint64_t>((a.n + 3) / 4, 4096), 256, 0, s>>>(a);
+    LAUNCHED(s, "segments_combine_kernel");
+  }
+  // the append's finish over the entries' total lengths
+  AppendArgs f{};
+  f.len = a.len;
+  f.kh = d_key_hashes;
+  f.n = a.n;
+  f.tail = tail;
+  f.base = a.base;
+  f.pre = a.pre;
+  f.cnt = a.cnt;
+  f.crc = a.crc;
+  f.nz = a.nz;
+  f.file = d_file;
+  f.mo = d_mo;
+  append_finish_kernel<<<(unsigned)std::min<uint64_t>((a.n + 255) / 256, 4096), 256, 0, s>>>(f);
+  LAUNCHED(s, "append_finish_kernel");
+  return 0;
+}
+
+extern "C" int srd_batch_append_segments_device(srd_ctx* c, const uint8_t* const* src_ptrs, const uint64_t* src_lens,
+                                                uint64_t n_src, const srd_segment* d_segs, uint64_t n_segs,
+                                                const uint64_t* d_seg_first, const uint64_t* d_key_hashes, uint64_t n,
+                                                uint32_t flags, uint64_t tail, uint8_t* d_file, uint64_t file_cap,
+                                                uint64_t* new_tail, uint64_t* d_meta_off_out, void* stream) {
+  if (!c || !new_tail || ((uintptr_t)d_file & 15) || (n_src && (!src_ptrs || !src_lens)) || (n_segs && !d_segs) ||
+      (n && (!d_seg_first || !d_key_hashes || !d_file || !d_meta_off_out))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  *new_tail = tail;
+  if (flags) { set_err("bad argument: flags must be 0"); return SRD_ERR_ARG; }
+  if (n >= (1ull << 31)) { set_err("too many entries in one batch"); return SRD_ERR_ARG; }
+  if (n_segs >= (1ull << 31)) { set_err("too many segments in one batch"); return SRD_ERR_ARG; }
+  if (n_src >= (1ull << 32)) { set_err("too many sources in one batch"); return SRD_ERR_ARG; }
+  if (!n) return 0;
+  std::vector<uint64_t> srcs(2 * n_src);
+  for (uint64_t k = 0; k < n_src; k++) {
+    if (src_lens[k] && !src_ptrs[k]) { set_err("bad argument: source " + std::to_string(k) + " is NULL"); return SRD_ERR_ARG; }
+    srcs[2 * k] = (uint64_t)(uintptr_t)src_ptrs[k];
+    srcs[2 * k + 1] = src_lens[k];
+  }
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream_of(c, stream);
+  SegmentsPlan p{};
+  TRY(segments_plan(c, s, srcs, d_segs, n_segs, d_seg_first, n, tail, &p));
+  const uint64_t nt = p.new_tail;
+  if (srd_padded_size(nt) > file_cap) {
+    set_err("file_cap too small for the batch: it ends at " + std::to_string(nt));
+    return SRD_ERR_ARG;
+  }
+  for (uint64_t k = 0; k < n_src; k++) {  // no source may lie in what the call writes
+    const uintptr_t p0 = (uintptr_t)srcs[2 * k], len = (uintptr_t)srcs[2 * k + 1];
+    const uintptr_t w0 = (uintptr_t)d_file + tail, w1 = (uintptr_t)d_file + gather_pad64(nt);
+    if (len && p0 < w1 && (w0 < p0 || w0 - p0 < len)) {  // (p0 + len may not be formed: it could wrap)
+      set_err("source " + std::to_string(k) + " overlaps the bytes the batch writes");
+      return SRD_ERR_ARG;
+    }
+  }
+  TRY(segments_commit(c, s, &p, d_key_hashes, tail, d_file, d_meta_off_out));
+  unsigned long long null_only = 0;  // the second wait: write_stream's check comes after the bytes
+  TRY(read_small(c, s, {rd(p.a.cnt + 4, &null_only)}));
+  TRY(append_null_only(null_only));
   *new_tail = nt;
   return 0;
 }

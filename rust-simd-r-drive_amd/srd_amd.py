@@ -72,6 +72,7 @@ EXPORTS = [
     "srd_stream_probe_device", "srd_ctx_multi_shard_ms",
     "srd_index_table_apply_device", "srd_index_table_export_device", "srd_batch_delete_hashed_device",
     "srd_payload_gather_device", "srd_batch_append_device", "srd_compact_live_device",
+    "srd_batch_append_segments_device",
 ]
 
 
@@ -120,6 +121,11 @@ class CompactStats(C.Structure):
 
     def __repr__(self):
         return "CompactStats(" + ", ".join(f"{n}={int(getattr(self, n))}" for n, _ in self._fields_) + ")"
+
+
+class Segment(C.Structure):
+    """srd_segment (include/srd_amd.h): the bytes sources[src][off : off + len]"""
+    _fields_ = [("src", C.c_uint32), ("reserved", C.c_uint32), ("off", C.c_uint64), ("len", C.c_uint64)]
 
 
 def build_info() -> str:
@@ -211,6 +217,8 @@ def lib():
         L.srd_payload_gather_device.argtypes = [vp, vp, u64, vp, vp, u64, u32, vp, u64, vp, vp, vp,
                                                 C.POINTER(u64), vp]
         L.srd_batch_append_device.argtypes = [vp, vp, u64, vp, vp, vp, u64, u32, u64, vp, u64, C.POINTER(u64), vp, vp]
+        L.srd_batch_append_segments_device.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), u64, vp, u64, vp, vp, u64, u32,
+                                                       u64, vp, u64, C.POINTER(u64), vp, vp]
         L.srd_compact_live_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(CompactStats)]
         L.srd_iter_entries_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
         L.srd_estimate_compaction_savings_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
@@ -988,6 +996,30 @@ def batch_append_device(d_payloads: int, payloads_len: int, d_src_off: int, d_le
     return int(nt.value)
 
 
+def batch_append_segments_device(src_ptrs, src_lens, d_segs: int, n_segs: int, d_seg_first: int, d_key_hashes: int,
+                                 n: int, tail: int, d_file: int, file_cap: int, d_meta_off_out: int,
+                                 ctx: "Context | None" = None, stream: int | None = None, flags: int = 0) -> int:
+    """srd_batch_append_segments_device as it is (the source table as host
+    sequences of device addresses and lengths, device pointers for the rest, the
+    new tail out): ordered on `stream` (default: the context stream), waits
+    twice.  SrdError carries the refusal's message and `.rc`."""
+    ctx = ctx or default_ctx()
+    _same_len(src_ptrs, src_lens, "source pointers and source lengths")
+    k = len(src_ptrs)
+    ptrs = (C.c_void_p * max(k, 1))(*[int(p) for p in src_ptrs])
+    lens = (C.c_uint64 * max(k, 1))(*[int(x) for x in src_lens])
+    nt = C.c_uint64()
+    rc = lib().srd_batch_append_segments_device(ctx.h, ptrs, lens, k, C.c_void_p(d_segs), n_segs, C.c_void_p(d_seg_first),
+                                                C.c_void_p(d_key_hashes), n, flags, tail, C.c_void_p(d_file), file_cap,
+                                                C.byref(nt), C.c_void_p(d_meta_off_out),
+                                                C.c_void_p(stream if stream is not None else ctx.stream))
+    if rc != 0:
+        e = SrdError(f"srd error {rc}: {lib().srd_last_error().decode()}")
+        e.rc = rc
+        raise e
+    return int(nt.value)
+
+
 class DeviceIndex:
     """The KeyIndexer adopted on the GPU: an open-addressing table in HBM built
     from n unique (key_hash, packed) device pairs -- e.g. the index arrays of a
@@ -1397,6 +1429,76 @@ class DeviceStore:
         if not len(keys):
             return self._tail
         return self.batch_write_device_with_key_hashes(compute_hash_batch(keys, self.ctx), blob, offs, lens)
+
+    # -- writes of payloads that arrive as a sequence of device segments ----------------------
+
+    def batch_write_stream_with_key_hashes(self, hashes, entries) -> int:
+        """n write_stream_with_key_hash calls (data_store.rs:758-825) for payloads
+        that arrive in pieces in HBM: entries[i] is a sequence of contiguous
+        tensors of any dtype on the store's device, taken as their bytes, in
+        order (a tensor of no bytes adds nothing; a slice of the store's own
+        buffer below the tail is allowed).  One source per distinct (data_ptr,
+        nbytes); the layout, the copy and the checksums over the pieces run on
+        the device (srd_batch_append_segments_device), then the reindex.  Returns
+        the new tail.  Anything that is not such a tensor raises ValueError
+        before any call, as does a batch beyond the capacity; the library's
+        refusals (an empty payload, one that is all NULL bytes, ...) raise
+        SrdError with the reference's message; the tail and the index are
+        unchanged then."""
+        import torch
+        _same_len(hashes, entries, "key hashes and entries")
+        n = len(entries)
+        if not n:
+            return self._tail
+        dev = self.buf.device
+        srcs, keep = {}, []
+        segs, first = [], [0]
+        for ent in entries:
+            if isinstance(ent, torch.Tensor) or isinstance(ent, (bytes, bytearray, str)):
+                raise ValueError("an entry must be a sequence of tensors")
+            for t in ent:
+                if not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous():
+                    raise ValueError("a segment must be a contiguous tensor on the store's device")
+                nb = t.numel() * t.element_size()
+                k = srcs.setdefault((t.data_ptr(), nb), len(srcs))
+                keep.append(t)
+                segs.append((k, 0, 0, nb))
+            first.append(len(segs))
+        seg_arr = (Segment * max(len(segs), 1))(*segs)
+        d_segs = torch.from_numpy(np.frombuffer(seg_arr, np.uint8).copy()).to(dev)
+        d_first = self.index._as_dev(np.array(first, np.uint64))
+        d_hashes = self.index._as_dev(hashes)
+        d_mo = torch.empty(n, dtype=torch.int64, device=dev)
+        self.index._lib_after_torch()
+        try:
+            new_tail = batch_append_segments_device([p for p, _ in srcs], [nb for _, nb in srcs], d_segs.data_ptr(),
+                                                    len(segs), d_first.data_ptr(), d_hashes.data_ptr(), n, self._tail,
+                                                    self.buf.data_ptr(), self.buf.numel(), d_mo.data_ptr(), self.ctx)
+        except SrdError as e:
+            self.index._sync_lib()  # (the inputs may be temporaries of the caller)
+            if e.rc == SRD_ERR_ARG and "file_cap" in str(e):
+                raise ValueError("the batch ends beyond the store's capacity") from e
+            raise
+        self.index.apply(d_hashes, d_mo)  # same stream: behind the append; waits
+        self._tail = new_tail
+        del keep
+        return new_tail
+
+    def batch_write_stream(self, keys, entries) -> int:
+        """write_stream (data_store.rs:753-756) of every key: compute_hash_batch,
+        then batch_write_stream_with_key_hashes."""
+        _same_len(keys, entries, "keys and entries")
+        if not len(keys):
+            return self._tail
+        return self.batch_write_stream_with_key_hashes(compute_hash_batch(keys, self.ctx), entries)
+
+    def write_stream_with_key_hash(self, key_hash: int, segments) -> int:
+        """write_stream_with_key_hash (data_store.rs:758-825): one entry from its segments."""
+        return self.batch_write_stream_with_key_hashes([key_hash], [segments])
+
+    def write_stream(self, key: bytes, segments) -> int:
+        """write_stream (data_store.rs:753-756)."""
+        return self.batch_write_stream([key], [segments])
 
     # -- copy / transfer / rename (data_store.rs:941-984): write_stream of the read entry ---
 
