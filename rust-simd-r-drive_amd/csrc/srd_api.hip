@@ -12,12 +12,16 @@
 //     srd_glue.hip            sync-free glue of the optimistic pass (shape test, entry pass), bucketed index, owner partition
 //     srd_writer.hip          batch writer
 //     srd_gather.h            the payload gather's range rule, unit / chunk arithmetic and CRC combine (a CPU check uses it too)
-//     srd_gather.hip          verified payloads: batched gather with checksum check (uses the writer's helpers)
 //     srd_append.h            the device append's range rule, layout and refusals (a CPU check uses it too)
-//     srd_append.hip          payloads in HBM appended to a store: layout and finish around the gather's kernels
-//     srd_segments.h          the segment append's table rule, unit cut, unit descriptor and CRC combine (a CPU check uses it too)
-//     srd_segments.hip        entries made of device segments appended to a store: layout, units, the streaming
-//                             kernel for any source / destination alignment, combine (around the append's finish)
+//     srd_segments.h          the segment append's table rule, unit cut and CRC combine; the unit descriptor and the
+//                             frame of the streaming kernel (a CPU check uses it too)
+//     srd_stream.hip          the streaming copy + CRC kernel, one wave per unit descriptor, for any source /
+//                             destination alignment: the gather's, both appends' and the live compaction's
+//                             (uses the writer's helpers)
+//     srd_gather.hip          verified payloads: layout, chunk units, combine and finish around the streaming kernel
+//     srd_append.hip          payloads in HBM appended to a store: layout and finish around the gather's units
+//     srd_segments.hip        entries made of device segments appended to a store: layout, units, combine (around
+//                             the append's finish)
 //     srd_table.h             the lookup table's rule: slot states, probe, claim, size arithmetic (the host entries
 //                             and a CPU check use it too)
 //     srd_index.hip           lookup table build and reads, iterator, compaction
@@ -63,10 +67,11 @@
 #include "srd_glue.hip"
 #include "srd_writer.hip"
 #include "srd_gather.h"
-#include "srd_gather.hip"
 #include "srd_append.h"
-#include "srd_append.hip"
 #include "srd_segments.h"
+#include "srd_stream.hip"
+#include "srd_gather.hip"
+#include "srd_append.hip"
 #include "srd_segments.hip"
 #include "srd_table.h"
 #include "srd_index.hip"

@@ -7,17 +7,17 @@
 //   (copy / transfer / rename go through it: :941-984, copy_handle :587-590)
 //
 // The write-side mirror of the gather: the layout is one exclusive sum on the
-// device (srd_append.h), the payload bytes move in the gather's work units by
-// the gather's own kernels -- the "file" is the caller's blob, the "output"
-// the store from roundup64(tail) on, the output offsets the layout's prefix --
-// and only what an append has on top of a copy is new.  Steps, all on the
-// caller's stream:
+// device (srd_append.h), the payload bytes move in the gather's work units
+// (PayloadRanges: the ranges are the payloads inside the caller's blob, the
+// output offsets the layout's prefix from roundup64(tail) on) through the
+// streaming kernel, and only what an append has on top of a copy is new.
+// Steps, all on the caller's stream:
 //   append_layout_kernel     per entry: status by arithmetic (one byte read
 //                            for a 1-byte payload), slot size, chunk count, the
 //                            source range's end (then two hipCUB exclusive sums)
 //   payload_units_kernel     the gather's unit table
-//   payload_gather_kernel    the gather's streaming kernel (<true> under the
-//                            stream rule: marks the entries that are not all 0)
+//   stream_copy_crc_kernel   the streaming kernel (srd_stream.hip; <true> under
+//                            the stream rule: marks the entries that are not all 0)
 //   payload_combine_kernel   the gather's fold of a multi-chunk entry's CRCs
 //   append_finish_kernel     per entry: the 20 metadata bytes, the zero prepad
 //                            up to the next payload, the metadata offset

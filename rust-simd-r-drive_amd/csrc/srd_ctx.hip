@@ -236,10 +236,11 @@ enum BufId {
   B_XKEY, B_XVAL, B_GATHER, B_RFLAG, B_O_PACKED, B_VSCAN, B_LOOKB, B_PROBE, B_XTOT,
   B_LV_DSLOT, B_LV_DTOMB, B_LV_LSLOT, B_LV_OPS, B_LV_OPV, B_LV_CNT,  // live table: apply
   B_LV_XK, B_LV_XP, B_LV_FLAG, B_LV_POS, B_LV_ENT, B_LV_TOMB,        // export, batched delete
-  B_GA_ST, B_GA_PLEN, B_GA_CHK, B_GA_OFF, B_GA_CPRE, B_GA_CNT, B_GA_UNIT, B_GA_RAW, B_GA_CRC,  // payload gather
+  B_GA_ST, B_GA_PLEN, B_GA_CHK, B_GA_OFF, B_GA_CPRE, B_GA_CNT, B_GA_RAW, B_GA_CRC,  // payload gather
+  B_ST_UNIT,  // the streaming kernel's unit descriptors, whoever builds them
   B_AP_END, B_AP_NZ,  // device append (on top of the gather's)
   B_CL_XK, B_CL_XP, B_CL_LEN, B_CL_MO, B_CL_PACKED, B_CL_CNT,  // live compaction (on top of the export's, the iterator's and the append's)
-  B_SG_SRC, B_SG_LEN, B_SG_OFF, B_SG_UN, B_SG_UPRE, B_SG_ENT, B_SG_UNIT,  // segment append (on top of the append's)
+  B_SG_SRC, B_SG_LEN, B_SG_OFF, B_SG_UN, B_SG_UPRE, B_SG_ENT,  // segment append (on top of the append's)
   B_COUNT_
 };
 

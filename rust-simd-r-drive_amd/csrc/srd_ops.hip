@@ -652,8 +652,37 @@ extern "C" int srd_compact_device(srd_ctx* c, const uint8_t* d_file, uint64_t fl
 }
 
 // ---------------------------------------------------------------------------
+// The streaming kernel (srd_stream.hip) over a unit table: one wave per unit up
+// to the scan's grid, with the stream rule's OR where there is an nz array
+static int launch_stream(Ctx* c, hipStream_t s, const StreamArgs& a) {
+  const unsigned g = (unsigned)std::min<uint64_t>((a.n_units + SCAN_WAVES_V2 - 1) / SCAN_WAVES_V2, c->scan_blocks);
+  if (a.nz) stream_copy_crc_kernel<true><<<g, SCAN_WAVES_V2 * 64, 0, s>>>(a);
+  else stream_copy_crc_kernel<false><<<g, SCAN_WAVES_V2 * 64, 0, s>>>(a);
+  LAUNCHED(s, "stream_copy_crc_kernel");
+  return 0;
+}
+
+// A batch of ranges moved in chunk units (srd_gather.hip): the unit table, the
+// streaming kernel into out (nullptr: verify only) and the combine for the
+// n_multi ranges of more than one chunk (units < 2^32: the caller's check)
+static int stream_chunks(Ctx* c, hipStream_t s, PayloadRanges r, uint64_t units, uint64_t n_multi, uint8_t* out,
+                         uint32_t* nz) {
+  TRY(ensure(c, B_ST_UNIT, units * sizeof(SegUnit)));
+  TRY(ensure(c, B_GA_RAW, units * 4));
+  r.unit = P<SegUnit>(c, B_ST_UNIT);
+  r.n_units = units;
+  r.raw = P<uint32_t>(c, B_GA_RAW);
+  payload_units_kernel<<<grid_for(units), 256, 0, s>>>(r);
+  LAUNCHED(s, "payload_units_kernel");
+  TRY(launch_stream(c, s, StreamArgs{r.unit, units, out, r.raw, r.crc, nz}));
+  if (n_multi) payload_combine_kernel<<<(unsigned)std::min<uint64_t>((r.n + 3) / 4, 4096), 256, 0, s>>>(r);
+  LAUNCHED(s, "payload_combine_kernel");
+  return 0;
+}
+
 // Verified payloads (srd_gather.hip): layout, one wait for the totals, then the
-// unit table, the gather, the combine and the finish enqueued on the stream
+// unit table, the streaming kernel, the combine and the finish enqueued on the
+// stream
 extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint64_t flen, const uint64_t* d_start,
                                          const uint64_t* d_end, uint64_t n, uint32_t flags, uint8_t* d_out,
                                          uint64_t out_cap, uint64_t* d_out_off, uint8_t* d_status,
@@ -698,9 +727,9 @@ extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint
   a.chk = P<uint64_t>(c, B_GA_CHK);
   a.off = P<uint64_t>(c, B_GA_OFF);
   a.cpre = P<uint64_t>(c, B_GA_CPRE);
+  a.pad = true;  // each hit's zero bytes up to the 64-byte boundary of the packed output
   a.cnt = P<unsigned long long>(c, B_GA_CNT);
   a.crc = P<uint32_t>(c, B_GA_CRC);
-  a.out = d_out;
   a.o_off = d_out_off;
   a.o_status = d_status;
   a.o_crc = d_crc_computed;
@@ -722,63 +751,40 @@ extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint
     return SRD_ERR_ARG;
   }
   if (units >= (1ull << 32)) { set_err("too many work units in one batch"); return SRD_ERR_ARG; }
-  if (!a.layout_only && units) {
-    TRY(ensure(c, B_GA_UNIT, units * 4));
-    TRY(ensure(c, B_GA_RAW, units * 4));
-    a.unit_hit = P<uint32_t>(c, B_GA_UNIT);
-    a.raw = P<uint32_t>(c, B_GA_RAW);
-    a.n_units = units;
-    payload_units_kernel<<<grid_for(units), 256, 0, s>>>(a);
-    LAUNCHED(s, "payload_units_kernel");
-    const unsigned g = (unsigned)std::min<uint64_t>((units + SCAN_WAVES_V2 - 1) / SCAN_WAVES_V2, c->scan_blocks);
-    payload_gather_kernel<<<g, SCAN_WAVES_V2 * 64, 0, s>>>(a);
-    LAUNCHED(s, "payload_gather_kernel");
-    if (n_multi) payload_combine_kernel<<<(unsigned)std::min<uint64_t>((n + 3) / 4, 4096), 256, 0, s>>>(a);
-    LAUNCHED(s, "payload_combine_kernel");
-  }
+  if (!a.layout_only && units) TRY(stream_chunks(c, s, a, units, n_multi, d_out, nullptr));
   payload_finish_kernel<<<grid_for(n + 1), 256, 0, s>>>(a);
   LAUNCHED(s, "payload_finish_kernel");
   return 0;
 }
 
 // ---------------------------------------------------------------------------
-// Payloads already in HBM appended to a store (srd_append.hip): layout, one
-// wait for the error word, the new tail and the unit counts, then the gather's
-// unit table, streaming kernel and combine with the store as their output,
-// and the finish enqueued on the stream.  Two steps over device arrays, which
-// srd_batch_append_device and srd_compact_live_device both run: append_plan
-// decides (nothing of the store is written), append_commit enqueues the writes.
+// Entries appended to a store from bytes already in HBM: the device append
+// (srd_append.hip; srd_compact_live_device runs it too) and the segment append
+// (srd_segments.hip).  Two steps each: the plan runs the owner's layout kernel
+// and exclusive sums and waits once for the error word, the new tail and the
+// unit counts (nothing of the store is written); the commit enqueues the unit
+// table, the streaming kernel, the combine and the finish.
 struct AppendPlan {
-  AppendArgs a;  // (file and mo: append_commit's)
+  AppendArgs a;  // the layout's and the finish's arguments (file and mo: append_finish's)
+  SegArgs g;     // the segment append's tables on top of them
   uint64_t new_tail, units, n_multi;
 };
+struct PlanWords { unsigned long long n_multi, err, coarse, len_last; };  // a.cnt[0 .. 4) read back
 
-// The layout kernel, the two exclusive sums and the one wait; SRD_ERR_ARG with
-// the refusal's message for what the entries themselves decide (n < 2^31: the
-// caller's check; it fits hipCUB's int count)
-static int append_plan(Ctx* c, hipStream_t s, const uint8_t* d_payloads, uint64_t payloads_len,
-                       const uint64_t* d_src_off, const uint64_t* d_len, const uint64_t* d_key_hashes, uint64_t n,
-                       bool rule, uint64_t tail, AppendPlan* p) {
+// The workspace and arguments both layouts share, the counter words at their
+// start values (n < 2^31: the caller's check; it fits hipCUB's int count)
+static int plan_begin(Ctx* c, hipStream_t s, AppendPlan* p, uint64_t n, uint64_t tail, bool rule) {
   TRY(ensure(c, B_GA_PLEN, n * 8));
   TRY(ensure(c, B_GA_CHK, n * 8));
   TRY(ensure(c, B_GA_OFF, n * 8));
-  TRY(ensure(c, B_GA_CPRE, n * 8));
   TRY(ensure(c, B_GA_CRC, n * 4));
   TRY(ensure(c, B_GA_CNT, 64));
-  TRY(ensure(c, B_AP_END, n * 8));
   if (rule) TRY(ensure(c, B_AP_NZ, n * 4));
-  TRY(ensure_scan(c, (const uint64_t*)nullptr, (uint64_t*)nullptr, n));  // both scans below
+  *p = AppendPlan{};
   AppendArgs& a = p->a;
-  a = AppendArgs{};
-  a.pay = d_payloads;
-  a.pay_len = payloads_len;
-  a.src = d_src_off;
-  a.len = d_len;
-  a.kh = d_key_hashes;
   a.n = n;
   a.tail = tail;
   a.base = append_base(tail);
-  a.end = P<uint64_t>(c, B_AP_END);
   a.slot = P<uint64_t>(c, B_GA_PLEN);
   a.chk = P<uint64_t>(c, B_GA_CHK);
   a.pre = P<uint64_t>(c, B_GA_OFF);
@@ -788,11 +794,66 @@ static int append_plan(Ctx* c, hipStream_t s, const uint8_t* d_payloads, uint64_
   HIPCHK(hipMemsetAsync(a.cnt, 0, 40, s));
   HIPCHK(hipMemsetAsync(a.cnt + 1, 0xFF, 8, s));  // the error word: none
   if (rule) HIPCHK(hipMemsetAsync(P<void>(c, B_AP_NZ), 0, n * 4, s));
+  return 0;
+}
+// ... and, once the owner has turned an error word into its message, what the
+// host decides from the words read back: the new tail
+static int plan_end(AppendPlan* p, const PlanWords& h, uint64_t pre_last) {
+  if (!append_new_tail(p->a.tail, h.coarse, pre_last, h.len_last, &p->new_tail)) {
+    set_err("the batch would end at 2^48 or beyond (the index packs 48-bit offsets)");
+    return SRD_ERR_ARG;
+  }
+  p->n_multi = h.n_multi;
+  return 0;
+}
+static int append_fits(uint64_t new_tail, uint64_t file_cap) {
+  if (srd_padded_size(new_tail) <= file_cap) return 0;
+  set_err("file_cap too small for the batch: it ends at " + std::to_string(new_tail));
+  return SRD_ERR_ARG;
+}
+// per entry: the metadata, the prepad, the caller's metadata offsets, the stream rule's outcome
+static int append_finish(hipStream_t s, AppendPlan* p, uint8_t* d_file, uint64_t* d_mo) {
+  AppendArgs& a = p->a;
+  a.file = d_file;
+  a.mo = d_mo;
+  append_finish_kernel<<<(unsigned)std::min<uint64_t>((a.n + 255) / 256, 4096), 256, 0, s>>>(a);
+  LAUNCHED(s, "append_finish_kernel");
+  return 0;
+}
+// write_stream's check comes after the bytes (data_store.rs:783-797)
+static int append_null_only(unsigned long long null_only) {
+  if (!null_only) return 0;
+  set_err("NULL-byte-only streams cannot be written directly.");
+  return SRD_ERR_ARG;
+}
+// the second wait: the rule's outcome is in a.cnt[4] once the stream has run
+static int append_rule_wait(Ctx* c, hipStream_t s, const AppendPlan& p) {
+  unsigned long long null_only = 0;
+  TRY(read_small(c, s, {rd(p.a.cnt + 4, &null_only)}));
+  return append_null_only(null_only);
+}
+
+// The append's plan: SRD_ERR_ARG with the refusal's message for what the
+// entries themselves decide
+static int append_plan(Ctx* c, hipStream_t s, const uint8_t* d_payloads, uint64_t payloads_len,
+                       const uint64_t* d_src_off, const uint64_t* d_len, const uint64_t* d_key_hashes, uint64_t n,
+                       bool rule, uint64_t tail, AppendPlan* p) {
+  TRY(plan_begin(c, s, p, n, tail, rule));
+  TRY(ensure(c, B_GA_CPRE, n * 8));
+  TRY(ensure(c, B_AP_END, n * 8));
+  TRY(ensure_scan(c, (const uint64_t*)nullptr, (uint64_t*)nullptr, n));  // both scans below
+  AppendArgs& a = p->a;
+  a.pay = d_payloads;
+  a.pay_len = payloads_len;
+  a.src = d_src_off;
+  a.len = d_len;
+  a.kh = d_key_hashes;
+  a.end = P<uint64_t>(c, B_AP_END);
   append_layout_kernel<<<grid_for(n), 256, 0, s>>>(a);
   LAUNCHED(s, "append_layout_kernel");
   // everything the host decides on, on one wait
   uint64_t pre_last = 0;
-  struct { unsigned long long n_multi, err, coarse, len_last; } h{};
+  PlanWords h{};
   TRY(scan_sum(c, (const uint64_t*)a.slot, P<uint64_t>(c, B_GA_OFF), n, s));
   TRY(scan_sum_total(c, (const uint64_t*)a.chk, P<uint64_t>(c, B_GA_CPRE), n, s, &p->units, rd(a.pre + n - 1, &pre_last),
                      SmallRead{a.cnt, &h, sizeof h}));
@@ -804,61 +865,28 @@ static int append_plan(Ctx* c, hipStream_t s, const uint8_t* d_payloads, uint64_
                                      : "the batch would end at 2^48 or beyond (the index packs 48-bit offsets)");
     return SRD_ERR_ARG;
   }
-  if (!append_new_tail(tail, h.coarse, pre_last, h.len_last, &p->new_tail)) {
-    set_err("the batch would end at 2^48 or beyond (the index packs 48-bit offsets)");
-    return SRD_ERR_ARG;
-  }
-  p->n_multi = h.n_multi;
-  return 0;
+  return plan_end(p, h, pre_last);
 }
 
-// The planned batch written to d_file (file byte j at d_file[j]) and its
-// metadata offsets to d_mo, enqueued on s; the one refusal left (too many
-// units) comes before anything is written.  Under the rule the outcome is in
-// a.cnt[4] once the stream has run: the caller's wait (append_null_only).
+// The planned batch written to d_file (file byte j at d_file[j], 16-byte
+// aligned) and its metadata offsets to d_mo, enqueued on s; the one refusal
+// left (too many units) comes before anything is written.  The payloads are
+// ranges of the blob, their output offsets the layout's prefix from base on.
 static int append_commit(Ctx* c, hipStream_t s, AppendPlan* p, uint8_t* d_file, uint64_t* d_mo) {
-  AppendArgs& a = p->a;
-  a.file = d_file;
-  a.mo = d_mo;
-  const uint64_t units = p->units;
-  if (units >= (1ull << 32)) { set_err("too many work units in one batch"); return SRD_ERR_ARG; }
-  TRY(ensure(c, B_GA_UNIT, units * 4));
-  TRY(ensure(c, B_GA_RAW, units * 4));
-  // the gather's kernels: the blob is their file, the store from base on their
-  // output, the layout's prefix their output offsets (64-aligned: base + pre)
-  PayloadGatherArgs ga{};
-  ga.file = a.pay;
-  ga.flen = a.pay_len;
-  ga.start = a.src;
-  ga.end = a.end;
-  ga.n = a.n;
-  ga.chk = a.chk;
-  ga.off = P<uint64_t>(c, B_GA_OFF);
-  ga.cpre = P<uint64_t>(c, B_GA_CPRE);
-  ga.unit_hit = P<uint32_t>(c, B_GA_UNIT);
-  ga.n_units = units;
-  ga.raw = P<uint32_t>(c, B_GA_RAW);
-  ga.crc = P<uint32_t>(c, B_GA_CRC);
-  ga.out = d_file + a.base;
-  ga.nz = P<uint32_t>(c, B_AP_NZ);
-  payload_units_kernel<<<grid_for(units), 256, 0, s>>>(ga);
-  LAUNCHED(s, "payload_units_kernel");
-  const unsigned g = (unsigned)std::min<uint64_t>((units + SCAN_WAVES_V2 - 1) / SCAN_WAVES_V2, c->scan_blocks);
-  if (a.nz) payload_gather_kernel<true><<<g, SCAN_WAVES_V2 * 64, 0, s>>>(ga);
-  else payload_gather_kernel<<<g, SCAN_WAVES_V2 * 64, 0, s>>>(ga);
-  LAUNCHED(s, "payload_gather_kernel");
-  if (p->n_multi) payload_combine_kernel<<<(unsigned)std::min<uint64_t>((a.n + 3) / 4, 4096), 256, 0, s>>>(ga);
-  LAUNCHED(s, "payload_combine_kernel");
-  append_finish_kernel<<<(unsigned)std::min<uint64_t>((a.n + 255) / 256, 4096), 256, 0, s>>>(a);
-  LAUNCHED(s, "append_finish_kernel");
-  return 0;
-}
-
-// write_stream's check comes after the bytes (data_store.rs:783-797)
-static int append_null_only(unsigned long long null_only) {
-  if (!null_only) return 0;
-  set_err("NULL-byte-only streams cannot be written directly.");
-  return SRD_ERR_ARG;
+  const AppendArgs& a = p->a;
+  if (p->units >= (1ull << 32)) { set_err("too many work units in one batch"); return SRD_ERR_ARG; }
+  PayloadRanges r{};
+  r.file = a.pay;
+  r.start = a.src;
+  r.end = a.end;
+  r.n = a.n;
+  r.chk = a.chk;
+  r.off = P<uint64_t>(c, B_GA_OFF);
+  r.cpre = P<uint64_t>(c, B_GA_CPRE);
+  r.dst0 = a.base;
+  r.crc = P<uint32_t>(c, B_GA_CRC);
+  TRY(stream_chunks(c, s, r, p->units, p->n_multi, d_file, const_cast<uint32_t*>(a.nz)));
+  return append_finish(s, p, d_file, d_mo);
 }
 
 extern "C" int srd_batch_append_device(srd_ctx* c, const uint8_t* d_payloads, uint64_t payloads_len,
@@ -879,46 +907,23 @@ extern "C" int srd_batch_append_device(srd_ctx* c, const uint8_t* d_payloads, ui
   AppendPlan p{};
   TRY(append_plan(c, s, d_payloads, payloads_len, d_src_off, d_len, d_key_hashes, n, rule, tail, &p));
   const uint64_t nt = p.new_tail;
-  if (srd_padded_size(nt) > file_cap) {
-    set_err("file_cap too small for the batch: it ends at " + std::to_string(nt));
-    return SRD_ERR_ARG;
-  }
+  TRY(append_fits(nt, file_cap));
   {  // the blob may not lie in what the call writes
     const uintptr_t p0 = (uintptr_t)d_payloads, p1 = p0 + payloads_len;
     const uintptr_t w0 = (uintptr_t)d_file + tail, w1 = (uintptr_t)d_file + gather_pad64(nt);
     if (payloads_len && p0 < w1 && w0 < p1) { set_err("d_payloads overlaps the bytes the batch writes"); return SRD_ERR_ARG; }
   }
   TRY(append_commit(c, s, &p, d_file, d_meta_off_out));
-  if (rule) {  // the second wait
-    unsigned long long null_only = 0;
-    TRY(read_small(c, s, {rd(p.a.cnt + 4, &null_only)}));
-    TRY(append_null_only(null_only));
-  }
+  if (rule) TRY(append_rule_wait(c, s, p));
   *new_tail = nt;
   return 0;
 }
 
-// ---------------------------------------------------------------------------
-// Entries made of device segments appended to a store (srd_segments.hip): the
-// append's two steps with a payload that arrives in pieces.  segments_plan
-// uploads the source table, runs the layout kernel and the two exclusive sums
-// (the entries' slots, the segments' unit counts) and waits once for the error
-// word, the new tail and the unit counts; segments_commit enqueues the unit
-// descriptors, the streaming kernel, the combine and the append's finish.
-struct SegmentsPlan {
-  SegArgs a;
-  uint64_t new_tail, units, n_multi;
-};
-
+// The segment append's plan: uploads the source table; the sums are the
+// entries' slots and the segments' unit counts
 static int segments_plan(Ctx* c, hipStream_t s, const std::vector<uint64_t>& srcs, const srd_segment* d_segs,
-                         uint64_t n_segs, const uint64_t* d_seg_first, uint64_t n, uint64_t tail, SegmentsPlan* p) {
-  const uint64_t n_src = srcs.size() / 2;
-  TRY(ensure(c, B_GA_PLEN, n * 8));
-  TRY(ensure(c, B_GA_CHK, n * 8));
-  TRY(ensure(c, B_GA_OFF, n * 8));
-  TRY(ensure(c, B_GA_CRC, n * 4));
-  TRY(ensure(c, B_GA_CNT, 64));
-  TRY(ensure(c, B_AP_NZ, n * 4));
+                         uint64_t n_segs, const uint64_t* d_seg_first, uint64_t n, uint64_t tail, AppendPlan* p) {
+  TRY(plan_begin(c, s, p, n, tail, true));
   TRY(ensure(c, B_SG_SRC, srcs.size() * 8));
   TRY(ensure(c, B_SG_LEN, n * 8));
   TRY(ensure(c, B_SG_OFF, n_segs * 8));
@@ -926,38 +931,34 @@ static int segments_plan(Ctx* c, hipStream_t s, const std::vector<uint64_t>& src
   TRY(ensure(c, B_SG_UPRE, n_segs * 8));
   TRY(ensure(c, B_SG_ENT, n_segs * 4));
   TRY(ensure_scan(c, (const uint64_t*)nullptr, (uint64_t*)nullptr, std::max(n, n_segs)));  // both scans below
-  SegArgs& a = p->a;
-  a = SegArgs{};
+  SegArgs& a = p->g;
   a.srcs = P<uint64_t>(c, B_SG_SRC);
-  a.n_src = n_src;
+  a.n_src = srcs.size() / 2;
   a.segs = d_segs;
   a.n_segs = n_segs;
   a.first = d_seg_first;
   a.n = n;
-  a.base = append_base(tail);
+  a.base = p->a.base;
   a.len = P<uint64_t>(c, B_SG_LEN);
-  a.slot = P<uint64_t>(c, B_GA_PLEN);
-  a.eun = P<uint64_t>(c, B_GA_CHK);
-  a.pre = P<uint64_t>(c, B_GA_OFF);
+  a.slot = p->a.slot;
+  a.eun = p->a.chk;
+  a.pre = p->a.pre;
   a.soff = P<uint64_t>(c, B_SG_OFF);
   a.sun = P<uint64_t>(c, B_SG_UN);
   a.upre = P<uint64_t>(c, B_SG_UPRE);
   a.sent = P<uint32_t>(c, B_SG_ENT);
-  a.cnt = P<unsigned long long>(c, B_GA_CNT);
+  a.cnt = p->a.cnt;
   a.crc = P<uint32_t>(c, B_GA_CRC);
   a.nz = P<uint32_t>(c, B_AP_NZ);
+  p->a.len = a.len;  // (the finish runs over the entries' total lengths)
   // (the table is the caller's for the call: the wait below comes before the return)
-  if (n_src) HIPCHK(hipMemcpyAsync(P<void>(c, B_SG_SRC), srcs.data(), srcs.size() * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(a.cnt, 0, 40, s));
-  HIPCHK(hipMemsetAsync(a.cnt + 1, 0xFF, 8, s));  // the error word: none
-  HIPCHK(hipMemsetAsync(a.nz, 0, n * 4, s));
+  if (a.n_src) HIPCHK(hipMemcpyAsync(P<void>(c, B_SG_SRC), srcs.data(), srcs.size() * 8, hipMemcpyHostToDevice, s));
   if (n_segs) HIPCHK(hipMemsetAsync(a.sun, 0, n_segs * 8, s));  // (a refused entry leaves its segments' counts alone)
   segments_layout_kernel<<<grid_for(n), 256, 0, s>>>(a);
   LAUNCHED(s, "segments_layout_kernel");
   // everything the host decides on, on one wait
   uint64_t pre_last = 0;
-  struct { unsigned long long n_multi, err, coarse, len_last; } h{};
-  p->units = 0;
+  PlanWords h{};
   if (n_segs) {
     TRY(scan_sum(c, (const uint64_t*)a.slot, P<uint64_t>(c, B_GA_OFF), n, s));
     TRY(scan_sum_total(c, (const uint64_t*)a.sun, P<uint64_t>(c, B_SG_UPRE), n_segs, s, &p->units,
@@ -974,52 +975,30 @@ static int segments_plan(Ctx* c, hipStream_t s, const std::vector<uint64_t>& src
                                     : "entry " + i + " is 2^48 bytes or longer (the index packs 48-bit offsets)");
     return SRD_ERR_ARG;
   }
-  if (!append_new_tail(tail, h.coarse, pre_last, h.len_last, &p->new_tail)) {
-    set_err("the batch would end at 2^48 or beyond (the index packs 48-bit offsets)");
-    return SRD_ERR_ARG;
-  }
-  p->n_multi = h.n_multi;
-  return 0;
+  return plan_end(p, h, pre_last);
 }
 
-static int segments_commit(Ctx* c, hipStream_t s, SegmentsPlan* p, const uint64_t* d_key_hashes, uint64_t tail,
-                           uint8_t* d_file, uint64_t* d_mo) {
-  SegArgs& a = p->a;
+static int segments_commit(Ctx* c, hipStream_t s, AppendPlan* p, const uint64_t* d_key_hashes, uint8_t* d_file,
+                           uint64_t* d_mo) {
+  SegArgs& a = p->g;
   const uint64_t units = p->units;
   if (units >= (1ull << 32)) { set_err("too many work units in one batch"); return SRD_ERR_ARG; }
-  TRY(ensure(c, B_SG_UNIT, units * sizeof(SegUnit)));
+  TRY(ensure(c, B_ST_UNIT, units * sizeof(SegUnit)));
   TRY(ensure(c, B_GA_RAW, units * 4));
-  a.unit = P<SegUnit>(c, B_SG_UNIT);
+  a.unit = P<SegUnit>(c, B_ST_UNIT);
   a.n_units = units;
   a.raw = P<uint32_t>(c, B_GA_RAW);
-  a.file = d_file;
   segments_units_kernel<<<grid_for(units), 256, 0, s>>>(a);
   LAUNCHED(s, "segments_units_kernel");
-  const unsigned g = (unsigned)std::min<uint64_t>((units + SCAN_WAVES_V2 - 1) / SCAN_WAVES_V2, c->scan_blocks);
-  segments_stream_kernel<<<g, SCAN_WAVES_V2 * 64, 0, s>>>(a);
-  LAUNCHED(s, "segments_stream_kernel");
+  TRY(launch_stream(c, s, StreamArgs{a.unit, units, d_file, a.raw, a.crc, a.nz}));
   if (p->n_multi) {
     segments_terms_kernel<<<grid_for(units), 256, 0, s>>>(a);
     LAUNCHED(s, "segments_terms_kernel");
     segments_combine_kernel<<<(unsigned)std::min<uint64_t>((a.n + 3) / 4, 4096), 256, 0, s>>>(a);
     LAUNCHED(s, "segments_combine_kernel");
   }
-  // the append's finish over the entries' total lengths
-  AppendArgs f{};
-  f.len = a.len;
-  f.kh = d_key_hashes;
-  f.n = a.n;
-  f.tail = tail;
-  f.base = a.base;
-  f.pre = a.pre;
-  f.cnt = a.cnt;
-  f.crc = a.crc;
-  f.nz = a.nz;
-  f.file = d_file;
-  f.mo = d_mo;
-  append_finish_kernel<<<(unsigned)std::min<uint64_t>((a.n + 255) / 256, 4096), 256, 0, s>>>(f);
-  LAUNCHED(s, "append_finish_kernel");
-  return 0;
+  p->a.kh = d_key_hashes;
+  return append_finish(s, p, d_file, d_mo);
 }
 
 extern "C" int srd_batch_append_segments_device(srd_ctx* c, const uint8_t* const* src_ptrs, const uint64_t* src_lens,
@@ -1046,13 +1025,10 @@ extern "C" int srd_batch_append_segments_device(srd_ctx* c, const uint8_t* const
   }
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = stream_of(c, stream);
-  SegmentsPlan p{};
+  AppendPlan p{};
   TRY(segments_plan(c, s, srcs, d_segs, n_segs, d_seg_first, n, tail, &p));
   const uint64_t nt = p.new_tail;
-  if (srd_padded_size(nt) > file_cap) {
-    set_err("file_cap too small for the batch: it ends at " + std::to_string(nt));
-    return SRD_ERR_ARG;
-  }
+  TRY(append_fits(nt, file_cap));
   for (uint64_t k = 0; k < n_src; k++) {  // no source may lie in what the call writes
     const uintptr_t p0 = (uintptr_t)srcs[2 * k], len = (uintptr_t)srcs[2 * k + 1];
     const uintptr_t w0 = (uintptr_t)d_file + tail, w1 = (uintptr_t)d_file + gather_pad64(nt);
@@ -1061,10 +1037,8 @@ extern "C" int srd_batch_append_segments_device(srd_ctx* c, const uint8_t* const
       return SRD_ERR_ARG;
     }
   }
-  TRY(segments_commit(c, s, &p, d_key_hashes, tail, d_file, d_meta_off_out));
-  unsigned long long null_only = 0;  // the second wait: write_stream's check comes after the bytes
-  TRY(read_small(c, s, {rd(p.a.cnt + 4, &null_only)}));
-  TRY(append_null_only(null_only));
+  TRY(segments_commit(c, s, &p, d_key_hashes, d_file, d_meta_off_out));
+  TRY(append_rule_wait(c, s, p));
   *new_tail = nt;
   return 0;
 }

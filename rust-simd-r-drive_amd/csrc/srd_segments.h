@@ -1,11 +1,15 @@
 // srd_segments.h -- the arithmetic of srd_batch_append_segments_device: how a
 // segment table is judged, how an entry's segments are cut into work units,
 // what a unit's descriptor holds, and how an entry's CRC-32 is put together
-// from its units' raw CRCs.  Plain integer code shared by the layout / unit /
-// combine kernels (srd_segments.hip), the host glue (srd_ops.hip) and a CPU
-// check (tests/sanitize_segments/segments_check.cpp): outside HIP the
-// qualifiers are empty.  The entry layout (slots, base, the new tail, the
-// error word) is the append's (srd_append.h) as it is.
+// from its units' raw CRCs.  The unit descriptor (SegUnit) and its frame are
+// also what the streaming kernel (srd_stream.hip) runs over for every caller:
+// the gather and the append describe their chunk units with it
+// (seg_chunk_unit).  Plain integer code shared by the layout / unit / combine
+// kernels (srd_segments.hip, srd_gather.hip), the streaming kernel, the host
+// glue (srd_ops.hip) and a CPU check (tests/sanitize_segments/
+// segments_check.cpp): outside HIP the qualifiers are empty.  The entry layout
+// (slots, base, the new tail, the error word) is the append's (srd_append.h) as
+// it is.
 //
 // Entry i's payload is the concatenation of segments first[i] .. first[i + 1);
 // segment s of it starts at offset seg_off[s] inside the entry, i.e. at file
@@ -100,8 +104,11 @@ struct SegUnit {
 static_assert(sizeof(SegUnit) == 32, "read as eight scalar words");
 // lf: bits 0-16 the length (1 .. C), bits 20-24 / 25-29 how many bytes of the
 // SEGMENT lie below the unit's first / behind its last byte (capped at 16: all
-// an aligned 16-byte load can reach), bit 31: the entry's only unit
+// an aligned 16-byte load can reach), bit 30: the unit owns the zero bytes from
+// its end up to the next 64-byte boundary of the output (SEG_LF_PAD), bit 31:
+// the entry's only unit
 static_assert(GATHER_CHUNK <= (1u << 16), "a unit's length takes 17 bits of SegUnit::lf");
+constexpr uint32_t SEG_LF_PAD = 1u << 30;
 SRD_GA_HD uint32_t seg_unit_lf(uint64_t len, uint64_t below, uint64_t behind, bool single) {
   return (uint32_t)len | (uint32_t)(below < 16 ? below : 16) << 20 | (uint32_t)(behind < 16 ? behind : 16) << 25 |
          (single ? 1u << 31 : 0u);
@@ -118,6 +125,21 @@ SRD_GA_HD SegUnit seg_unit(uint64_t src_addr, uint64_t dst, uint64_t off, uint64
   uint64_t b0, b1;
   seg_unit_range(dst & 15, len, k, &b0, &b1);
   return SegUnit{src_addr + b0, dst + b0, off + b1, ent, seg_unit_lf(b1 - b0, b0, len - b1, ent_units == 1)};
+}
+// Chunk k of a hit or payload of len bytes and `chunks` chunks (srd_gather.h)
+// whose destination starts at a 64-byte boundary: the range is one segment
+// that is its own entry, so the cut is the chunk cut, the below / behind counts
+// are taken against the range itself, and end is the chunk's end inside it.
+// pad: the last chunk owns the zero bytes up to the next 64-byte boundary.
+SRD_GA_HD SegUnit seg_chunk_unit(uint64_t src_addr, uint64_t dst, uint64_t len, uint64_t k, uint32_t ent, uint64_t chunks,
+                                 bool pad) {
+  SegUnit x = seg_unit(src_addr, dst, 0, len, k, ent, chunks);
+  if (pad && k + 1 == chunks) x.lf |= SEG_LF_PAD;
+  return x;
+}
+// how many zero bytes a unit owns behind its end (output offsets of hits are multiples of 64)
+SRD_GA_HD uint32_t seg_unit_pad(uint64_t dst, uint32_t lf) {
+  return lf & SEG_LF_PAD ? (uint32_t)(0 - (dst + seg_lf_len(lf))) & 63u : 0u;
 }
 
 // The streaming kernel's frame of a unit, aligned to the DESTINATION: with a =

@@ -8,6 +8,8 @@
 //     the next unit's destination begins; every unit but a segment's first
 //     starts at a 16-byte boundary of the store;
 //   - a unit's descriptor never lets an aligned 16-byte load leave its segment;
+//   - the same for the chunk units of the gather and the append (a whole range
+//     as one segment) at every start residue, with the pad count of a last unit;
 //   - the XOR of the units' terms (bitwise host CRC per unit) is the CRC-32 of
 //     the concatenation (check value 0xCBF43926 included);
 //   - the entry layout equals srd_batch_layout's for the concatenated lengths
@@ -17,6 +19,7 @@
 // Exit status 0 = no sanitizer report and every invariant held.
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <random>
@@ -250,6 +253,45 @@ static void check_cut() {
   }
 }
 
+// Chunk units as the gather and the append build them (seg_chunk_unit): a whole
+// range [start, end) taken as one segment whose destination starts at a 64-byte
+// boundary.  At every start residue, for lengths around 16, 4096, C and 2 C:
+// the units are the range's chunks, every aligned source vector the streaming
+// kernel's walk admits lies inside [start, end) (check_frame; the range ends at
+// its allocation's end, so the sanitizer sees a read past it), and a range's
+// last unit owns the zero bytes up to the next 64-byte boundary when asked to.
+static uint64_t g_chunk_units = 0;
+static void check_chunk_units(std::mt19937_64& rng) {
+  const uint64_t lens[] = {1, 15, 16, 17, 31, 32, 33, 47, 48, 49, 4095, 4096, 4097, 4111, 4112, 4113, C - 17, C - 16,
+                           C - 1, C, C + 1, C + 15, C + 16, C + 17, 2 * C - 1, 2 * C, 2 * C + 1, 2 * C + 17};
+  for (uint64_t res = 0; res < 16; res++) {
+    for (uint64_t len : lens) {
+      uint8_t* exact = (uint8_t*)malloc(16 + res + len);  // (malloc aligns to 16: the range ends where the block ends)
+      EXPECT(exact && ((uintptr_t)exact & 15) == 0);
+      if (!exact || ((uintptr_t)exact & 15)) continue;
+      for (uint64_t j = 0; j < 16 + res + len; j++) exact[j] = (uint8_t)(rng() >> 56);
+      const uint64_t start = (uint64_t)(uintptr_t)exact + 16 + res;
+      const std::vector<uint8_t> copy(exact + 16 + res, exact + 16 + res + len);
+      const uint64_t chunks = gather_chunks(len), dst = 64 * (1 + rng() % 1000);
+      for (int pad = 0; pad < 2; pad++) {
+        for (uint64_t k = 0; k < chunks; k++) {
+          const SegUnit x = seg_chunk_unit(start, dst, len, k, 7, chunks, pad);
+          const uint64_t cl = gather_chunk_len(len, k);
+          EXPECT(x.src == start + k * C && x.dst == dst + k * C && seg_lf_len(x.lf) == cl && x.end == k * C + cl);
+          EXPECT(x.ent == 7 && seg_lf_single(x.lf) == (chunks == 1) && (x.dst & 15) == 0);
+          EXPECT(seg_lf_below(x.lf) == (k ? 16 : 0));
+          EXPECT(seg_lf_behind(x.lf) == (len - x.end < 16 ? len - x.end : 16));
+          EXPECT(seg_frame(x.src, x.dst, x.lf).r == (res & 15));
+          EXPECT(seg_unit_pad(x.dst, x.lf) == (pad && k + 1 == chunks ? gather_pad64(len) - len : 0));
+          check_frame(x, start, len, copy.data() + k * C);
+          g_chunk_units++;
+        }
+      }
+      free(exact);
+    }
+  }
+}
+
 static void check_crc_value(const CrcTables& t) {
   // "123456789" in three pieces behind a 5-byte piece of another source: CRC-32 0xCBF43926
   const uint8_t s[] = "123456789";
@@ -347,12 +389,14 @@ int main() {
   for (uint64_t res = 0; res < 64; res++)
     for (int it = 0; it < 3; it++) check_tables(t, rng, (rng() % 5000) * 64 + res, src);
   for (uint64_t res = 0; res < 64; res++) check_tables(t, rng, res, src);  // (a store of less than one line)
+  check_chunk_units(rng);
   check_refusals();
   if (g_fail) {
     fprintf(stderr, "segments_check: %d invariant(s) failed\n", g_fail);
     return 1;
   }
-  printf("segments_check ok: chunk %llu, %llu entries, %llu segments, %llu units\n", (unsigned long long)C,
-         (unsigned long long)g_entries, (unsigned long long)g_segs, (unsigned long long)g_units);
+  printf("segments_check ok: chunk %llu, %llu entries, %llu segments, %llu units, %llu chunk units\n", (unsigned long long)C,
+         (unsigned long long)g_entries, (unsigned long long)g_segs, (unsigned long long)g_units,
+         (unsigned long long)g_chunk_units);
   return 0;
 }

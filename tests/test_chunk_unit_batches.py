@@ -1,7 +1,7 @@
 """The batches tests/test_gpu_chunk_units.py runs, and what they must cover.
 
 A host restatement of the chunk units of srd_gather.h / srd_gather.hip -- how a
-batch's hits are cut into units, which wave of payload_gather_kernel's grid
+batch's hits are cut into units, which wave of stream_copy_crc_kernel's grid
 walks which units, and how payload_combine_kernel splits a hit's chunks over
 its 64 lanes -- plus the seeded generators of the batches.  The tests here need
 no GPU: they assert that the generated batches meet the coverage conditions
@@ -15,11 +15,11 @@ import pytest
 import srd_amd as S
 
 CH = S.GATHER_CHUNK
-TILE = 4096          # payload_gather_kernel's block
+TILE = 4096          # stream_copy_crc_kernel's block (srd_stream.hip)
 GATHER_LANES = 64    # srd_gather.h
-# SCAN_WAVES_V2 (srd_kernels.hip): the waves of one payload_gather_kernel block.  The grid is
-# min(ceil(units / SCAN_WAVES_V2), c->scan_blocks) blocks, scan_blocks = the CU count (the launch lines in
-# srd_payload_gather_device and append_commit, srd_ops.hip), so a batch of more than W = 16 x CUs units gives
+# SCAN_WAVES_V2 (srd_kernels.hip): the waves of one stream_copy_crc_kernel block.  The grid is
+# min(ceil(units / SCAN_WAVES_V2), c->scan_blocks) blocks, scan_blocks = the CU count (launch_stream,
+# srd_ops.hip, for srd_payload_gather_device and append_commit alike), so a batch of more than W = 16 x CUs units gives
 # wave w the units w, w + W, w + 2 W, ...
 WAVES_PER_BLOCK = 16
 GRIDS = [WAVES_PER_BLOCK * cus for cus in (64, 256, 304)]
@@ -120,7 +120,7 @@ def spaced_offsets(lens, seed=SEED):
 
 
 def unit_table(lens, srcs=None):
-    """The units of a batch in query order, as payload_gather_kernel's unit_s sees them: per unit its hit, its
+    """The units of a batch in query order, as stream_copy_crc_kernel's unit_s sees them: per unit its hit, its
     4 KiB block count, whether its source address is 16-byte aligned (srcs: byte offsets from a 16-aligned base),
     and its role in the hit."""
     lens = np.asarray(lens, np.int64)

@@ -236,8 +236,11 @@ def test_start_tail_residues(ctx, res):
 # -- source alignment ---------------------------------------------------------------------
 
 @pytest.mark.parametrize("base_shift", [0, 1])
-@pytest.mark.parametrize("residue", [0, 1, 8, 15])
+@pytest.mark.parametrize("residue", range(16))
 def test_source_alignment(ctx, residue, base_shift):
+    """Every source residue mod 16 against the 64-aligned payload slots: the
+    streaming kernel's one-vector path (residue + base_shift a multiple of 16)
+    and each shift of its two-vector path."""
     rng = random.Random(16 * base_shift + residue)
     payloads = [nonzero_bytes(rng, n) for n in (17, 1040, 4097, 12289, CH + 1, 2 * CH + 17)]
     hashes = [kh(b"al-%d" % i) for i in range(len(payloads))]

@@ -1,5 +1,5 @@
 """Chunk units at many chunks per hit and many units per wave: the shapes of
-payload_units_kernel / payload_gather_kernel / payload_combine_kernel that the
+payload_units_kernel / stream_copy_crc_kernel / payload_combine_kernel that the
 length lists of test_gpu_gather.py, test_gpu_append.py and
 test_gpu_compact_live.py do not reach, through all three callers
 (srd_payload_gather_device, srd_batch_append_device, DeviceStore.compact).
@@ -47,8 +47,8 @@ def ctx():
 
 @pytest.fixture(scope="module")
 def W():
-    """The waves of payload_gather_kernel's grid once a batch has a unit for each: SCAN_WAVES_V2 = 16 per block,
-    one block per CU (U.WAVES_PER_BLOCK names the launch lines)."""
+    """The waves of stream_copy_crc_kernel's grid once a batch has a unit for each: SCAN_WAVES_V2 = 16 per block,
+    one block per CU (U.WAVES_PER_BLOCK names the launch line)."""
     import torch
     return U.WAVES_PER_BLOCK * torch.cuda.get_device_properties(0).multi_processor_count
 

@@ -309,6 +309,76 @@ def test_caller_made_ranges(ctx, lstore):
     assert [int(x) for x in r.crc] == [O.crc32(p) if p is not None else 0 for p in want]
 
 
+REALIGN_LENGTHS = [1, 15, 16, 17, 33, 4095, 4097, CH + 1, 2 * CH + 17]
+
+
+@pytest.fixture(scope="module")
+def realign_hits():
+    """Hand-made hits at every start residue mod 16 and every length of
+    REALIGN_LENGTHS: random payload bytes, 16 arbitrary bytes, the little-endian
+    CRC-32 of the payload at end + 16.  (file bytes, [(start, end)], [payload])"""
+    rng = random.Random(0xA116)
+    buf, ranges, pays = bytearray(rng.randbytes(7)), [], []
+    for res in range(16):
+        for n in REALIGN_LENGTHS:
+            buf += rng.randbytes(1 + (res - len(buf) - 1) % 16)  # (at least one byte between two hits)
+            assert len(buf) % 16 == res
+            p = rng.randbytes(n)
+            ranges.append((len(buf), len(buf) + n))
+            pays.append(p)
+            buf += p + rng.randbytes(16) + O.crc32(p).to_bytes(4, "little")
+    return bytes(buf), ranges, pays
+
+
+def shifted_dev(f, shift):
+    """The file on the device at an address that is `shift` mod 16."""
+    import torch
+    dev = torch.zeros(S.padded_size(len(f)) + 64, dtype=torch.uint8, device="cuda")
+    assert dev.data_ptr() % 16 == 0
+    dev[shift: shift + len(f)] = torch.frombuffer(bytearray(f), dtype=torch.uint8).cuda()
+    torch.cuda.synchronize()
+    return dev, dev.data_ptr() + shift
+
+
+@pytest.mark.parametrize("shift", [0, 1])
+def test_realigned_sources(ctx, realign_hits, shift):
+    """Sources that are not 16-byte aligned to the packed output (every start
+    residue, the file base aligned and not): the streaming kernel assembles each
+    destination vector from two source vectors.  A copying and a verify-only
+    call; bytes, padding, statuses and CRCs against the oracle."""
+    import torch
+    f, ranges, pays = realign_hits
+    dev, d_file = shifted_dev(f, shift)
+    st, en = [a for a, _ in ranges], [b for _, b in ranges]
+    crc_want = [O.crc32(p) for p in pays]
+    r = Raw(ctx, d_file, len(f), st, en)
+    assert r.rc == 0
+    assert list(r.status) == [S.GATHER_OK] * len(pays) and [int(x) for x in r.crc] == crc_want
+    check_packed(r.out, r.offs, r.total, pays)
+    sentinel = torch.full((r.total + SLACK,), FILL, dtype=torch.uint8, device="cuda")
+    v = Raw(ctx, d_file, len(f), st, en, S.GATHER_VERIFY_ONLY, out=sentinel, cap=sentinel.numel())
+    assert v.rc == 0
+    assert list(v.status) == [S.GATHER_OK] * len(pays) and [int(x) for x in v.crc] == crc_want
+    assert (v.out == FILL).all()
+
+
+def test_realigned_flip_is_reported(ctx, realign_hits):
+    """One flipped byte in the second chunk of a multi-chunk hit at start
+    residue 5: that status, and only that one, is BAD_CRC."""
+    f, ranges, pays = realign_hits
+    i = 5 * len(REALIGN_LENGTHS) + REALIGN_LENGTHS.index(2 * CH + 17)
+    assert ranges[i][0] % 16 == 5 and ranges[i][1] - ranges[i][0] == 2 * CH + 17
+    g = bytearray(f)
+    g[ranges[i][0] + CH + 100] ^= 0x10
+    flipped = [bytes(g[a:b]) for a, b in ranges]
+    dev, d_file = shifted_dev(bytes(g), 1)
+    r = Raw(ctx, d_file, len(f), [a for a, _ in ranges], [b for _, b in ranges])
+    assert r.rc == 0
+    assert list(r.status) == [S.GATHER_BAD_CRC if j == i else S.GATHER_OK for j in range(len(pays))]
+    assert [int(x) for x in r.crc] == [O.crc32(p) for p in flipped]
+    check_packed(r.out, r.offs, r.total, flipped)
+
+
 def test_many_units_per_wave(ctx):
     import torch
     n = 300_000

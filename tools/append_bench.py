@@ -16,7 +16,10 @@ one host wait is inside its window) and with the host clock ending in a
 synchronise; warm-ups first, then median [min, max].  Every case first checks
 that the append and the writer produced the same store bytes.  One JSON line.
 
-usage: python tools/append_bench.py [--cases acde] [--reps R] [--warmup W] [--out FILE]"""
+--src-residue K moves every payload K bytes up inside the blob (K = 1..15: no
+source is 16-byte aligned to its destination slot).
+
+usage: python tools/append_bench.py [--cases acde] [--reps R] [--warmup W] [--src-residue K] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -45,8 +48,8 @@ def gbps(nbytes, st):
 
 
 class Bench:
-    def __init__(self, ctx):
-        self.ctx, self.L = ctx, S.lib()
+    def __init__(self, ctx, residue=0):
+        self.ctx, self.L, self.residue = ctx, S.lib(), residue
         self.stream = torch.cuda.ExternalStream(ctx.stream)
 
     def timed(self, fn):
@@ -60,12 +63,12 @@ class Bench:
         return e0.elapsed_time(e1), (time.perf_counter() - t0) * 1e3
 
     def case(self, n, length, reps, warmup, writer_reps=None):
-        """n payloads of `length` bytes, back to back at 16-byte boundaries of one device blob."""
+        """n payloads of `length` bytes, back to back at 16-byte boundaries (+ the residue) of one device blob."""
         stride = (length + 15) & ~15
         lens = np.full(n, length, np.uint64)
-        offs = np.arange(n, dtype=np.uint64) * np.uint64(stride)
+        offs = np.arange(n, dtype=np.uint64) * np.uint64(stride) + np.uint64(self.residue)
         hashes = (np.arange(n, dtype=np.uint64) + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
-        blob = torch.randint(1, 256, (n * stride,), dtype=torch.uint8, device="cuda")
+        blob = torch.randint(1, 256, (n * stride + 16,), dtype=torch.uint8, device="cuda")
         nbytes = n * length
         # the writer's host layout and entry table (outside every timed window)
         ent = np.zeros(n, ENTRY)
@@ -102,7 +105,7 @@ class Bench:
             # torch's copy of a contiguous uint8 range on one device is the runtime's own
             # device-to-device hipMemcpyAsync, here on the context stream
             with torch.cuda.stream(self.stream):
-                out_w[:nbytes].copy_(blob[:nbytes])
+                out_w[:nbytes].copy_(blob[self.residue: self.residue + nbytes])
 
         plain, rule = append_fn(0), append_fn(S.APPEND_STREAM_RULE)
         # the same bytes and offsets from both paths, before anything is timed
@@ -137,11 +140,12 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--writer-reps-d", type=int, default=2)
+    ap.add_argument("--src-residue", type=int, default=0, choices=range(16))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     ctx = S.Context(0)
-    B = Bench(ctx)
-    res = {"chunk": S.GATHER_CHUNK, "lib": S.build_info(),
+    B = Bench(ctx, a.src_residue)
+    res = {"chunk": S.GATHER_CHUNK, "lib": S.build_info(), "src_residue": a.src_residue,
            "memcpy": "hipMemcpyAsync device-to-device (torch copy_ of a contiguous range)"}
     shapes = {"a": (1024, 4096, None), "c": (1 << 20, 4096, None), "d": (8, 256 << 20, a.writer_reps_d),
               "e": (1 << 20, 8, None)}
