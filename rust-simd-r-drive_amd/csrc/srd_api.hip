@@ -11,17 +11,22 @@
 //     srd_kernels.hip         scan, link, full-pass glue, finalize (one entry: finalize_in), slow path, batch digests, synth
 //     srd_glue.hip            sync-free glue of the optimistic pass (shape test, entry pass), bucketed index, owner partition
 //     srd_writer.hip          batch writer
-//     srd_gather.h            the payload gather's range rule, unit / chunk arithmetic and CRC combine (a CPU check uses it too)
+//     srd_gather.h            the payload gather's range rule, chunk arithmetic, unit search and the powers of x a
+//                             CRC is combined with (a CPU check uses it too)
 //     srd_append.h            the device append's range rule, layout and refusals (a CPU check uses it too)
-//     srd_segments.h          the segment append's table rule, unit cut and CRC combine; the unit descriptor and the
-//                             frame of the streaming kernel (a CPU check uses it too)
+//     srd_segments.h          the segment append's table rule and unit cut; for every caller the unit descriptor, the
+//                             batch cut into units (UnitArgs) under its two views, a unit's CRC term and the frame
+//                             of the streaming kernel (a CPU check uses it too)
 //     srd_stream.hip          the streaming copy + CRC kernel, one wave per unit descriptor, for any source /
 //                             destination alignment: the gather's, both appends' and the live compaction's
 //                             (uses the writer's helpers)
-//     srd_gather.hip          verified payloads: layout, chunk units, combine and finish around the streaming kernel
-//     srd_append.hip          payloads in HBM appended to a store: layout and finish around the gather's units
-//     srd_segments.hip        entries made of device segments appended to a store: layout, units, combine (around
-//                             the append's finish)
+//     srd_units.hip           the unit table and the CRC combine (terms, XOR) around the streaming kernel, for the
+//                             same callers
+//     srd_gather.hip          verified payloads: layout and finish around the unit kernels
+//     srd_append.hip          payloads in HBM appended to a store: layout (its second half shared with the segment
+//                             append's) and finish around the unit kernels
+//     srd_segments.hip        entries made of device segments appended to a store: layout (around the unit kernels
+//                             and the append's finish)
 //     srd_table.h             the lookup table's rule: slot states, probe, claim, size arithmetic (the host entries
 //                             and a CPU check use it too)
 //     srd_index.hip           lookup table build and reads, iterator, compaction
@@ -70,6 +75,7 @@
 #include "srd_append.h"
 #include "srd_segments.h"
 #include "srd_stream.hip"
+#include "srd_units.hip"
 #include "srd_gather.hip"
 #include "srd_append.hip"
 #include "srd_segments.hip"

@@ -3,8 +3,8 @@
 // refuse the batch.  Plain integer code shared by the layout / finish kernels
 // (srd_append.hip), the host glue (srd_ops.hip) and a CPU check
 // (tests/sanitize_append/append_check.cpp): outside HIP the qualifiers are
-// empty.  The work units, the unit table and the CRC combine are the gather's
-// (srd_gather.h) as they are.
+// empty.  The work units are the gather's chunks (srd_gather.h); the unit
+// table and the CRC combine are every caller's (srd_segments.h, UnitArgs).
 //
 // Layout (batch_write_with_key_hashes, data_store.rs:847-939, for payloads
 // that are no tombstones): with base = roundup64(tail), entry i has its

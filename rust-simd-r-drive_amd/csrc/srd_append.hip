@@ -8,17 +8,17 @@
 //
 // The write-side mirror of the gather: the layout is one exclusive sum on the
 // device (srd_append.h), the payload bytes move in the gather's work units
-// (PayloadRanges: the ranges are the payloads inside the caller's blob, the
-// output offsets the layout's prefix from roundup64(tail) on) through the
-// streaming kernel, and only what an append has on top of a copy is new.
+// (UnitArgs' ranges: the payloads inside the caller's blob, the output offsets
+// the layout's prefix from roundup64(tail) on) through the streaming kernel,
+// and only what an append has on top of a copy is new.
 // Steps, all on the caller's stream:
 //   append_layout_kernel     per entry: status by arithmetic (one byte read
 //                            for a 1-byte payload), slot size, chunk count, the
 //                            source range's end (then two hipCUB exclusive sums)
-//   payload_units_kernel     the gather's unit table
-//   stream_copy_crc_kernel   the streaming kernel (srd_stream.hip; <true> under
-//                            the stream rule: marks the entries that are not all 0)
-//   payload_combine_kernel   the gather's fold of a multi-chunk entry's CRCs
+//   units_kernel .. unit_combine_kernel   the unit table, the streaming kernel
+//                            (<true> under the stream rule: marks the entries
+//                            that are not all 0) and the combine (srd_units.hip),
+//                            the payloads as ranges
 //   append_finish_kernel     per entry: the 20 metadata bytes, the zero prepad
 //                            up to the next payload, the metadata offset
 
@@ -32,7 +32,7 @@ struct AppendArgs {
   uint64_t tail, base;  // base = append_base(tail)
   uint64_t* end;        // [n] src + len (the gather kernels' range end; 0 for a refused range)
   uint64_t* slot;       // [n] append_slot(len)
-  uint64_t* chk;        // [n] chunk count
+  uint64_t* chk;        // [n] unit count (UnitArgs::eun)
   const uint64_t* pre;  // [n] exclusive sum of slot
   // [0] entries of more than one chunk, [1] the error word (append_err_word:
   // atomicMin), [2] the sum of append_coarse(slot), [3] the last entry's
@@ -54,33 +54,53 @@ __device__ __forceinline__ uint64_t lane_u64(uint64_t v, int l) {
          (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)v, l);
 }
 
+// What both layout kernels (the segment append's: srd_segments.hip) do with an
+// entry once it is judged -- status st, len bytes, `units` units; every lane of
+// a wave comes here, the lanes past the batch (i >= n) too: the ballot sees 64
+// lanes -- its slot and unit count (none for a refused entry), the sums, the
+// last entry's length, and the count of the entries of more than one unit ...
+struct LayoutSums { uint64_t coarse = 0, err = ~0ull; };
+__device__ __forceinline__ void append_layout_entry(const AppendArgs& a, uint64_t i, uint32_t st, uint64_t len, uint64_t units,
+                                                    LayoutSums& t) {
+  uint64_t k = 0;
+  if (i < a.n) {
+    const bool ok = st == APPEND_OK;
+    const uint64_t slot = ok ? append_slot(len) : 0;
+    k = ok ? units : 0;
+    a.slot[i] = slot;
+    a.chk[i] = k;
+    t.coarse += append_coarse(slot);
+    if (!ok) t.err = min<uint64_t>(t.err, append_err_word(i, st));
+    if (i == a.n - 1) a.cnt[3] = len;
+  }
+  const uint64_t m = __ballot(k > 1);
+  if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(a.cnt, (unsigned long long)__builtin_popcountll(m));
+}
+// ... and, behind the last round, the error word and the coarse sum
+__device__ __forceinline__ void append_layout_close(const AppendArgs& a, LayoutSums t) {
+  if (t.err != ~0ull) atomicMin(a.cnt + 1, (unsigned long long)t.err);  // (a refused batch only)
+  t.coarse = wave_sum_u64(t.coarse);
+  if ((threadIdx.x & 63) == 0 && t.coarse) atomicAdd(a.cnt + 2, (unsigned long long)t.coarse);
+}
+
 __global__ __launch_bounds__(256) void append_layout_kernel(AppendArgs a) {
-  uint64_t coarse = 0, err = ~0ull;
+  LayoutSums sums;
   // (whole waves in every round: the ballot and the reductions see 64 lanes)
   const uint64_t rounds = (a.n + gridDim.x * 256ull - 1) / (gridDim.x * 256ull);
   for (uint64_t r = 0; r < rounds; r++) {
     const uint64_t i = (r * gridDim.x + blockIdx.x) * 256ull + threadIdx.x;
-    uint64_t k = 0;
+    uint64_t len = 0;
+    uint32_t st = APPEND_EMPTY;
     if (i < a.n) {
-      const uint64_t s = a.src[i], len = a.len[i];
-      uint32_t st = append_range_status(s, len, a.pay_len);
+      const uint64_t s = a.src[i];
+      len = a.len[i];
+      st = append_range_status(s, len, a.pay_len);
       if (st == APPEND_OK && len == 1 && a.pay[s] == 0) st = APPEND_NULL_BYTE;
-      const bool ok = st == APPEND_OK;
-      const uint64_t slot = ok ? append_slot(len) : 0;
-      k = ok ? gather_chunks(len) : 0;
-      a.end[i] = ok ? s + len : 0;
-      a.slot[i] = slot;
-      a.chk[i] = k;
-      coarse += append_coarse(slot);
-      if (!ok) err = min<uint64_t>(err, append_err_word(i, st));
-      if (i == a.n - 1) a.cnt[3] = len;
+      a.end[i] = st == APPEND_OK ? s + len : 0;
     }
-    const uint64_t m = __ballot(k > 1);
-    if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(a.cnt, (unsigned long long)__builtin_popcountll(m));
+    append_layout_entry(a, i, st, len, gather_chunks(len), sums);
   }
-  if (err != ~0ull) atomicMin(a.cnt + 1, (unsigned long long)err);  // (a refused batch only)
-  coarse = wave_sum_u64(coarse);
-  if ((threadIdx.x & 63) == 0 && coarse) atomicAdd(a.cnt + 2, (unsigned long long)coarse);
+  append_layout_close(a, sums);
 }
 
 // One wave per 64 consecutive entries: lane j loads entry i0 + j's layout (its

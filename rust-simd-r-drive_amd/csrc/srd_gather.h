@@ -1,9 +1,11 @@
 // srd_gather.h -- the arithmetic of srd_payload_gather_device: how a query's
 // range is judged, how hits are cut into work units (chunks), how a unit finds
-// its hit again, and how a hit's CRC-32 is put together from its chunks' raw
-// CRCs.  Plain integer code shared by the layout / unit-table / combine
-// kernels (srd_gather.hip) and a CPU check (tests/sanitize_gather/
-// gather_check.cpp): outside HIP the qualifiers are empty.
+// its hit again, and the powers of x a CRC-32 is put together with (a hit's is
+// combined from its chunks' raw CRCs as every entry's is: srd_segments.h,
+// seg_unit_term).  Plain integer code shared by the layout kernel
+// (srd_gather.hip), the unit kernels (srd_units.hip) and a CPU check
+// (tests/sanitize_gather/gather_check.cpp): outside HIP the qualifiers are
+// empty.
 //
 // A hit of len bytes has ceil(len / SRD_GATHER_CHUNK) chunks; chunk j covers
 // its bytes [j C, min(len, (j + 1) C)).  The units of a batch are the chunks of
@@ -29,7 +31,6 @@ namespace srd {
 
 constexpr uint64_t GATHER_CHUNK = SRD_GATHER_CHUNK;
 static_assert(GATHER_CHUNK >= 4096 && GATHER_CHUNK % 4096 == 0, "a unit is a whole number of 4 KiB blocks");
-constexpr int GATHER_LANES = 64;  // the combine's split of a hit's chunks over one wave
 
 // What the range alone decides: NONE, BAD_RANGE, or a hit (reported as OK
 // here; the checksum turns it into OK or BAD_CRC).  A hit lies inside the
@@ -69,48 +70,12 @@ SRD_GA_HD uint32_t gather_xpow8(P pow8, uint64_t n) {
   return r;
 }
 
-// crc_raw of the hit's bytes [j0 C, min(len, j1 C)) from the chunks' raw CRCs
-// raw[j0 .. j1): one Horner step per chunk, by x^(8 C) for a whole chunk and
-// by the last chunk's own length (j0 < j1 <= the hit's chunk count)
-template <class R, class P>
-SRD_GA_HD uint32_t gather_fold(R raw, uint64_t j0, uint64_t j1, uint64_t len, P pow8) {
-  const uint32_t xc = gather_xpow8(pow8, GATHER_CHUNK);
-  uint32_t acc = 0;
-  for (uint64_t j = j0; j < j1; j++) {
-    const uint64_t cl = gather_chunk_len(len, j);
-    acc = mulp(cl == GATHER_CHUNK ? xc : gather_xpow8(pow8, cl), acc) ^ raw[j];
-  }
-  return acc;
-}
-// the segment of lane l when k chunks are split over GATHER_LANES lanes:
-// chunks [l s, min(k, (l + 1) s)), s = ceil(k / GATHER_LANES)
-SRD_GA_HD void gather_lane_chunks(uint64_t k, uint32_t l, uint64_t* j0, uint64_t* j1) {
-  const uint64_t s = (k + GATHER_LANES - 1) / GATHER_LANES;
-  const uint64_t a = s * l, b = a + s;
-  *j0 = a < k ? a : k;
-  *j1 = b < k ? b : k;
-}
-// a lane's term of the hit's raw CRC: its segment's value moved up by the
-// bytes that follow the segment (the XOR over the lanes is crc_raw(hit))
-template <class R, class P>
-SRD_GA_HD uint32_t gather_lane_term(R raw, uint64_t k, uint32_t l, uint64_t len, P pow8) {
-  uint64_t j0, j1;
-  gather_lane_chunks(k, l, &j0, &j1);
-  if (j0 >= j1) return 0;
-  const uint64_t seg_end = j1 * GATHER_CHUNK < len ? j1 * GATHER_CHUNK : len;
-  return mulp(gather_xpow8(pow8, len - seg_end), gather_fold(raw, j0, j1, len, pow8));
-}
 // CRC32 from crc_raw: crc32fast's init and xorout 0xFFFFFFFF depend on the
 // length alone (srd_crc.h: CRC32(D) = crc_raw(D) ^ CRC32(0^|D|)), the fix the
 // batch writer applies
 template <class P>
 SRD_GA_HD uint32_t gather_final(uint32_t raw, uint64_t len, P pow8) {
   return raw ^ ~mulp(gather_xpow8(pow8, len), 0xFFFFFFFFu);
-}
-// a hit's CRC32 from its k chunks' raw CRCs, serially
-template <class R, class P>
-SRD_GA_HD uint32_t gather_combine(R raw, uint64_t k, uint64_t len, P pow8) {
-  return gather_final(gather_fold(raw, 0, k, len, pow8), len, pow8);
 }
 
 }  // namespace srd

@@ -17,34 +17,15 @@
 // distributed over the hits.  Steps, all on the caller's stream:
 //   payload_layout_kernel   per query: status by arithmetic, padded length,
 //                           chunk count (then two hipCUB exclusive sums)
-//   payload_units_kernel    the unit table: per chunk its descriptor (SegUnit)
-//   stream_copy_crc_kernel  one wave per unit: copy + raw CRC of the chunk (a
-//                           single-unit hit's CRC is finished here; srd_stream.hip)
-//   payload_combine_kernel  one wave per multi-unit hit: folds its chunks' CRCs
+//   units_kernel .. unit_combine_kernel   the unit table, the streaming kernel
+//                           and the combine (srd_units.hip), the hits as ranges
 //   payload_finish_kernel   per query: stored checksum, status, the caller's arrays
-// srd_batch_append_device (srd_append.hip) cuts its payloads into the same
-// units (PayloadRanges) and folds them with the same combine.
 
 namespace srd {
 
-// A batch of ranges cut into chunk units: what the unit table and the combine
-// need of it, whoever laid it out (the gather's hits, the append's payloads)
-struct PayloadRanges {
-  const uint8_t* file;          // the bytes the ranges index
-  const uint64_t *start, *end;  // the ranges [n]
-  uint64_t n;
-  uint64_t* chk;   // [n] chunk count
-  uint64_t* off;   // [n] the output offsets less dst0, multiples of 64
-  uint64_t* cpre;  // [n] exclusive sum of chk
-  uint64_t dst0;   // a multiple of 64
-  bool pad;        // a range's last unit zeroes up to the next 64-byte boundary of the output
-  SegUnit* unit;   // [n_units] the unit table
-  uint64_t n_units;
-  uint32_t* raw;   // [n_units] a multi-unit range's chunks: crc_raw
-  uint32_t* crc;   // [n] a range's CRC32
-};
-
-struct PayloadGatherArgs : PayloadRanges {  // (off = the exclusive sum of plen)
+// (the hits as UnitArgs' ranges: eun = the chunk counts, off = the exclusive
+// sum of plen, upre = the exclusive sum of the chunk counts)
+struct PayloadGatherArgs : UnitArgs {
   uint64_t flen;
   uint8_t* st;     // [n] gather_range_status
   uint64_t* plen;  // [n] padded length (0 for no hit)
@@ -65,34 +46,9 @@ __global__ __launch_bounds__(256) void payload_layout_kernel(PayloadGatherArgs a
     a.st[i] = (uint8_t)st;
     const uint64_t k = gather_chunks(len);
     a.plen[i] = gather_pad64(len);
-    a.chk[i] = k;
+    a.eun[i] = k;
     const uint64_t m = __ballot(k > 1);
     if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(a.cnt, (unsigned long long)__builtin_popcountll(m));
-  }
-}
-
-// unit u: chunk u - cpre[i] of the range i with cpre[i] <= u < cpre[i + 1]
-__global__ __launch_bounds__(256) void payload_units_kernel(PayloadRanges a) {
-  for (uint64_t u = blockIdx.x * 256ull + threadIdx.x; u < a.n_units; u += gridDim.x * 256ull) {
-    const uint64_t i = gather_unit_hit(a.cpre, a.n, u), s = a.start[i];
-    a.unit[u] = seg_chunk_unit((uint64_t)(uintptr_t)a.file + s, a.dst0 + a.off[i], a.end[i] - s, u - a.cpre[i], (uint32_t)i,
-                               a.chk[i], a.pad);
-  }
-}
-
-// One wave per hit of more than one chunk: lane l folds the raw CRCs of its
-// share of the chunks (gather_lane_term: Horner by x^(8 chunk), moved up by
-// the bytes behind the share), the XOR over the lanes is crc_raw(hit), and the
-// length-dependent init / xorout fix makes it the CRC32.
-__global__ __launch_bounds__(256) void payload_combine_kernel(PayloadRanges a) {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t W = gridDim.x * 4ull;
-  for (uint64_t i = blockIdx.x * 4ull + (threadIdx.x >> 6); i < a.n; i += W) {
-    const uint64_t k = a.chk[i];
-    if (k < 2) continue;  // (uniform per wave)
-    const uint64_t len = a.end[i] - a.start[i];
-    const uint32_t t = wave_xor(gather_lane_term(a.raw + a.cpre[i], k, lane, len, g_tabs.pow8));
-    if (lane == 0) a.crc[i] = gather_final(t, len, g_tabs.pow8);
   }
 }
 

@@ -662,22 +662,32 @@ static int launch_stream(Ctx* c, hipStream_t s, const StreamArgs& a) {
   return 0;
 }
 
-// A batch of ranges moved in chunk units (srd_gather.hip): the unit table, the
+// A batch of entries moved in units (srd_units.hip): the unit table, the
 // streaming kernel into out (nullptr: verify only) and the combine for the
-// n_multi ranges of more than one chunk (units < 2^32: the caller's check)
-static int stream_chunks(Ctx* c, hipStream_t s, PayloadRanges r, uint64_t units, uint64_t n_multi, uint8_t* out,
-                         uint32_t* nz) {
+// n_multi entries of more than one unit (units < 2^32: the caller's check)
+template <class View>
+static int stream_units_as(Ctx* c, hipStream_t s, UnitArgs a, uint64_t units, uint64_t n_multi, uint8_t* out, uint32_t* nz) {
   TRY(ensure(c, B_ST_UNIT, units * sizeof(SegUnit)));
   TRY(ensure(c, B_GA_RAW, units * 4));
-  r.unit = P<SegUnit>(c, B_ST_UNIT);
-  r.n_units = units;
-  r.raw = P<uint32_t>(c, B_GA_RAW);
-  payload_units_kernel<<<grid_for(units), 256, 0, s>>>(r);
-  LAUNCHED(s, "payload_units_kernel");
-  TRY(launch_stream(c, s, StreamArgs{r.unit, units, out, r.raw, r.crc, nz}));
-  if (n_multi) payload_combine_kernel<<<(unsigned)std::min<uint64_t>((r.n + 3) / 4, 4096), 256, 0, s>>>(r);
-  LAUNCHED(s, "payload_combine_kernel");
+  a.unit = P<SegUnit>(c, B_ST_UNIT);
+  a.n_units = units;
+  a.raw = P<uint32_t>(c, B_GA_RAW);
+  units_kernel<View><<<grid_for(units), 256, 0, s>>>(a);
+  LAUNCHED(s, "units_kernel");
+  TRY(launch_stream(c, s, StreamArgs{a.unit, units, out, a.raw, a.crc, nz}));
+  if (n_multi) {
+    unit_terms_kernel<View><<<grid_for(units), 256, 0, s>>>(a);
+    LAUNCHED(s, "unit_terms_kernel");
+    unit_combine_kernel<View><<<(unsigned)std::min<uint64_t>((a.n + 3) / 4, 4096), 256, 0, s>>>(a);
+    LAUNCHED(s, "unit_combine_kernel");
+  }
   return 0;
+}
+// (a batch with a segment table is read through it, any other as ranges)
+static int stream_units(Ctx* c, hipStream_t s, const UnitArgs& a, uint64_t units, uint64_t n_multi, uint8_t* out,
+                        uint32_t* nz) {
+  return a.segs ? stream_units_as<TableView>(c, s, a, units, n_multi, out, nz)
+                : stream_units_as<RangeView>(c, s, a, units, n_multi, out, nz);
 }
 
 // Verified payloads (srd_gather.hip): layout, one wait for the totals, then the
@@ -721,12 +731,12 @@ extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint
   a.flen = flen;
   a.start = d_start;
   a.end = d_end;
-  a.n = n;
+  a.n = a.n_segs = n;
   a.st = P<uint8_t>(c, B_GA_ST);
   a.plen = P<uint64_t>(c, B_GA_PLEN);
-  a.chk = P<uint64_t>(c, B_GA_CHK);
+  a.eun = P<uint64_t>(c, B_GA_CHK);
   a.off = P<uint64_t>(c, B_GA_OFF);
-  a.cpre = P<uint64_t>(c, B_GA_CPRE);
+  a.upre = P<uint64_t>(c, B_GA_CPRE);
   a.pad = true;  // each hit's zero bytes up to the 64-byte boundary of the packed output
   a.cnt = P<unsigned long long>(c, B_GA_CNT);
   a.crc = P<uint32_t>(c, B_GA_CRC);
@@ -741,7 +751,7 @@ extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint
   uint64_t off_last = 0, plen_last = 0, units = 0;
   unsigned long long n_multi = 0;
   TRY(scan_sum(c, (const uint64_t*)a.plen, a.off, n, s));
-  TRY(scan_sum_total(c, (const uint64_t*)a.chk, a.cpre, n, s, &units, rd(a.off + n - 1, &off_last),
+  TRY(scan_sum_total(c, (const uint64_t*)a.eun, a.upre, n, s, &units, rd(a.off + n - 1, &off_last),
                      rd(a.plen + n - 1, &plen_last), rd(a.cnt, &n_multi)));
   const uint64_t tot = off_last + plen_last;
   *total = tot;
@@ -751,7 +761,7 @@ extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint
     return SRD_ERR_ARG;
   }
   if (units >= (1ull << 32)) { set_err("too many work units in one batch"); return SRD_ERR_ARG; }
-  if (!a.layout_only && units) TRY(stream_chunks(c, s, a, units, n_multi, d_out, nullptr));
+  if (!a.layout_only && units) TRY(stream_units(c, s, a, units, n_multi, d_out, nullptr));
   payload_finish_kernel<<<grid_for(n + 1), 256, 0, s>>>(a);
   LAUNCHED(s, "payload_finish_kernel");
   return 0;
@@ -766,7 +776,7 @@ extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint
 // table, the streaming kernel, the combine and the finish.
 struct AppendPlan {
   AppendArgs a;  // the layout's and the finish's arguments (file and mo: append_finish's)
-  SegArgs g;     // the segment append's tables on top of them
+  UnitArgs u;    // the batch cut into units: the append's ranges, the segment append's table
   uint64_t new_tail, units, n_multi;
 };
 struct PlanWords { unsigned long long n_multi, err, coarse, len_last; };  // a.cnt[0 .. 4) read back
@@ -791,6 +801,12 @@ static int plan_begin(Ctx* c, hipStream_t s, AppendPlan* p, uint64_t n, uint64_t
   a.cnt = P<unsigned long long>(c, B_GA_CNT);
   a.crc = P<uint32_t>(c, B_GA_CRC);
   a.nz = rule ? P<uint32_t>(c, B_AP_NZ) : nullptr;
+  UnitArgs& u = p->u;  // (the layout's unit counts and prefix are what the unit kernels read)
+  u.n = n;
+  u.eun = a.chk;
+  u.off = P<uint64_t>(c, B_GA_OFF);
+  u.dst0 = a.base;
+  u.crc = P<uint32_t>(c, B_GA_CRC);
   HIPCHK(hipMemsetAsync(a.cnt, 0, 40, s));
   HIPCHK(hipMemsetAsync(a.cnt + 1, 0xFF, 8, s));  // the error word: none
   if (rule) HIPCHK(hipMemsetAsync(P<void>(c, B_AP_NZ), 0, n * 4, s));
@@ -849,13 +865,19 @@ static int append_plan(Ctx* c, hipStream_t s, const uint8_t* d_payloads, uint64_
   a.len = d_len;
   a.kh = d_key_hashes;
   a.end = P<uint64_t>(c, B_AP_END);
+  UnitArgs& u = p->u;  // the payloads as ranges of the blob
+  u.n_segs = n;
+  u.upre = P<uint64_t>(c, B_GA_CPRE);
+  u.file = d_payloads;
+  u.start = d_src_off;
+  u.end = a.end;
   append_layout_kernel<<<grid_for(n), 256, 0, s>>>(a);
   LAUNCHED(s, "append_layout_kernel");
   // everything the host decides on, on one wait
   uint64_t pre_last = 0;
   PlanWords h{};
   TRY(scan_sum(c, (const uint64_t*)a.slot, P<uint64_t>(c, B_GA_OFF), n, s));
-  TRY(scan_sum_total(c, (const uint64_t*)a.chk, P<uint64_t>(c, B_GA_CPRE), n, s, &p->units, rd(a.pre + n - 1, &pre_last),
+  TRY(scan_sum_total(c, (const uint64_t*)a.chk, u.upre, n, s, &p->units, rd(a.pre + n - 1, &pre_last),
                      SmallRead{a.cnt, &h, sizeof h}));
   if (h.err != ~0ull) {
     const uint32_t st = append_err_status(h.err);
@@ -870,22 +892,10 @@ static int append_plan(Ctx* c, hipStream_t s, const uint8_t* d_payloads, uint64_
 
 // The planned batch written to d_file (file byte j at d_file[j], 16-byte
 // aligned) and its metadata offsets to d_mo, enqueued on s; the one refusal
-// left (too many units) comes before anything is written.  The payloads are
-// ranges of the blob, their output offsets the layout's prefix from base on.
-static int append_commit(Ctx* c, hipStream_t s, AppendPlan* p, uint8_t* d_file, uint64_t* d_mo) {
-  const AppendArgs& a = p->a;
+// left (too many units) comes before anything is written.
+static int plan_commit(Ctx* c, hipStream_t s, AppendPlan* p, uint8_t* d_file, uint64_t* d_mo) {
   if (p->units >= (1ull << 32)) { set_err("too many work units in one batch"); return SRD_ERR_ARG; }
-  PayloadRanges r{};
-  r.file = a.pay;
-  r.start = a.src;
-  r.end = a.end;
-  r.n = a.n;
-  r.chk = a.chk;
-  r.off = P<uint64_t>(c, B_GA_OFF);
-  r.cpre = P<uint64_t>(c, B_GA_CPRE);
-  r.dst0 = a.base;
-  r.crc = P<uint32_t>(c, B_GA_CRC);
-  TRY(stream_chunks(c, s, r, p->units, p->n_multi, d_file, const_cast<uint32_t*>(a.nz)));
+  TRY(stream_units(c, s, p->u, p->units, p->n_multi, d_file, const_cast<uint32_t*>(p->a.nz)));
   return append_finish(s, p, d_file, d_mo);
 }
 
@@ -913,7 +923,7 @@ extern "C" int srd_batch_append_device(srd_ctx* c, const uint8_t* d_payloads, ui
     const uintptr_t w0 = (uintptr_t)d_file + tail, w1 = (uintptr_t)d_file + gather_pad64(nt);
     if (payloads_len && p0 < w1 && w0 < p1) { set_err("d_payloads overlaps the bytes the batch writes"); return SRD_ERR_ARG; }
   }
-  TRY(append_commit(c, s, &p, d_file, d_meta_off_out));
+  TRY(plan_commit(c, s, &p, d_file, d_meta_off_out));
   if (rule) TRY(append_rule_wait(c, s, p));
   *new_tail = nt;
   return 0;
@@ -922,7 +932,8 @@ extern "C" int srd_batch_append_device(srd_ctx* c, const uint8_t* d_payloads, ui
 // The segment append's plan: uploads the source table; the sums are the
 // entries' slots and the segments' unit counts
 static int segments_plan(Ctx* c, hipStream_t s, const std::vector<uint64_t>& srcs, const srd_segment* d_segs,
-                         uint64_t n_segs, const uint64_t* d_seg_first, uint64_t n, uint64_t tail, AppendPlan* p) {
+                         uint64_t n_segs, const uint64_t* d_seg_first, const uint64_t* d_key_hashes, uint64_t n,
+                         uint64_t tail, AppendPlan* p) {
   TRY(plan_begin(c, s, p, n, tail, true));
   TRY(ensure(c, B_SG_SRC, srcs.size() * 8));
   TRY(ensure(c, B_SG_LEN, n * 8));
@@ -931,37 +942,30 @@ static int segments_plan(Ctx* c, hipStream_t s, const std::vector<uint64_t>& src
   TRY(ensure(c, B_SG_UPRE, n_segs * 8));
   TRY(ensure(c, B_SG_ENT, n_segs * 4));
   TRY(ensure_scan(c, (const uint64_t*)nullptr, (uint64_t*)nullptr, std::max(n, n_segs)));  // both scans below
-  SegArgs& a = p->g;
-  a.srcs = P<uint64_t>(c, B_SG_SRC);
-  a.n_src = srcs.size() / 2;
-  a.segs = d_segs;
-  a.n_segs = n_segs;
-  a.first = d_seg_first;
-  a.n = n;
-  a.base = p->a.base;
-  a.len = P<uint64_t>(c, B_SG_LEN);
-  a.slot = p->a.slot;
-  a.eun = p->a.chk;
-  a.pre = p->a.pre;
-  a.soff = P<uint64_t>(c, B_SG_OFF);
-  a.sun = P<uint64_t>(c, B_SG_UN);
-  a.upre = P<uint64_t>(c, B_SG_UPRE);
-  a.sent = P<uint32_t>(c, B_SG_ENT);
-  a.cnt = p->a.cnt;
-  a.crc = P<uint32_t>(c, B_GA_CRC);
-  a.nz = P<uint32_t>(c, B_AP_NZ);
-  p->a.len = a.len;  // (the finish runs over the entries' total lengths)
+  AppendArgs& a = p->a;
+  UnitArgs& u = p->u;
+  u.n_segs = n_segs;
+  u.upre = P<uint64_t>(c, B_SG_UPRE);
+  u.srcs = P<uint64_t>(c, B_SG_SRC);
+  u.segs = d_segs;
+  u.first = d_seg_first;
+  u.len = P<uint64_t>(c, B_SG_LEN);
+  u.soff = P<uint64_t>(c, B_SG_OFF);
+  u.sun = P<uint64_t>(c, B_SG_UN);
+  u.sent = P<uint32_t>(c, B_SG_ENT);
+  a.len = u.len;  // (the finish runs over the entries' total lengths)
+  a.kh = d_key_hashes;
   // (the table is the caller's for the call: the wait below comes before the return)
-  if (a.n_src) HIPCHK(hipMemcpyAsync(P<void>(c, B_SG_SRC), srcs.data(), srcs.size() * 8, hipMemcpyHostToDevice, s));
-  if (n_segs) HIPCHK(hipMemsetAsync(a.sun, 0, n_segs * 8, s));  // (a refused entry leaves its segments' counts alone)
-  segments_layout_kernel<<<grid_for(n), 256, 0, s>>>(a);
+  if (!srcs.empty()) HIPCHK(hipMemcpyAsync(P<void>(c, B_SG_SRC), srcs.data(), srcs.size() * 8, hipMemcpyHostToDevice, s));
+  if (n_segs) HIPCHK(hipMemsetAsync(u.sun, 0, n_segs * 8, s));  // (a refused entry leaves its segments' counts alone)
+  segments_layout_kernel<<<grid_for(n), 256, 0, s>>>(a, u, srcs.size() / 2);
   LAUNCHED(s, "segments_layout_kernel");
   // everything the host decides on, on one wait
   uint64_t pre_last = 0;
   PlanWords h{};
   if (n_segs) {
     TRY(scan_sum(c, (const uint64_t*)a.slot, P<uint64_t>(c, B_GA_OFF), n, s));
-    TRY(scan_sum_total(c, (const uint64_t*)a.sun, P<uint64_t>(c, B_SG_UPRE), n_segs, s, &p->units,
+    TRY(scan_sum_total(c, (const uint64_t*)u.sun, u.upre, n_segs, s, &p->units,
                        rd(a.pre + n - 1, &pre_last), SmallRead{a.cnt, &h, sizeof h}));
   } else {
     TRY(read_small(c, s, {SmallRead{a.cnt, &h, sizeof h}}));  // (every entry is empty: refused below)
@@ -976,29 +980,6 @@ static int segments_plan(Ctx* c, hipStream_t s, const std::vector<uint64_t>& src
     return SRD_ERR_ARG;
   }
   return plan_end(p, h, pre_last);
-}
-
-static int segments_commit(Ctx* c, hipStream_t s, AppendPlan* p, const uint64_t* d_key_hashes, uint8_t* d_file,
-                           uint64_t* d_mo) {
-  SegArgs& a = p->g;
-  const uint64_t units = p->units;
-  if (units >= (1ull << 32)) { set_err("too many work units in one batch"); return SRD_ERR_ARG; }
-  TRY(ensure(c, B_ST_UNIT, units * sizeof(SegUnit)));
-  TRY(ensure(c, B_GA_RAW, units * 4));
-  a.unit = P<SegUnit>(c, B_ST_UNIT);
-  a.n_units = units;
-  a.raw = P<uint32_t>(c, B_GA_RAW);
-  segments_units_kernel<<<grid_for(units), 256, 0, s>>>(a);
-  LAUNCHED(s, "segments_units_kernel");
-  TRY(launch_stream(c, s, StreamArgs{a.unit, units, d_file, a.raw, a.crc, a.nz}));
-  if (p->n_multi) {
-    segments_terms_kernel<<<grid_for(units), 256, 0, s>>>(a);
-    LAUNCHED(s, "segments_terms_kernel");
-    segments_combine_kernel<<<(unsigned)std::min<uint64_t>((a.n + 3) / 4, 4096), 256, 0, s>>>(a);
-    LAUNCHED(s, "segments_combine_kernel");
-  }
-  p->a.kh = d_key_hashes;
-  return append_finish(s, p, d_file, d_mo);
 }
 
 extern "C" int srd_batch_append_segments_device(srd_ctx* c, const uint8_t* const* src_ptrs, const uint64_t* src_lens,
@@ -1026,7 +1007,7 @@ extern "C" int srd_batch_append_segments_device(srd_ctx* c, const uint8_t* const
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = stream_of(c, stream);
   AppendPlan p{};
-  TRY(segments_plan(c, s, srcs, d_segs, n_segs, d_seg_first, n, tail, &p));
+  TRY(segments_plan(c, s, srcs, d_segs, n_segs, d_seg_first, d_key_hashes, n, tail, &p));
   const uint64_t nt = p.new_tail;
   TRY(append_fits(nt, file_cap));
   for (uint64_t k = 0; k < n_src; k++) {  // no source may lie in what the call writes
@@ -1037,7 +1018,7 @@ extern "C" int srd_batch_append_segments_device(srd_ctx* c, const uint8_t* const
       return SRD_ERR_ARG;
     }
   }
-  TRY(segments_commit(c, s, &p, d_key_hashes, d_file, d_meta_off_out));
+  TRY(plan_commit(c, s, &p, d_file, d_meta_off_out));
   TRY(append_rule_wait(c, s, p));
   *new_tail = nt;
   return 0;
@@ -1120,7 +1101,7 @@ extern "C" int srd_compact_live_device(srd_ctx* c, const void* d_table, uint64_t
   TRY(ensure(c, B_CL_PACKED, nv * 8));
   TRY(ensure(c, B_CL_CNT, 64));
   unsigned long long* cnt = P<unsigned long long>(c, B_CL_CNT);
-  TRY(append_commit(c, s, &p, d_out, P<uint64_t>(c, B_CL_MO)));
+  TRY(plan_commit(c, s, &p, d_out, P<uint64_t>(c, B_CL_MO)));
   HIPCHK(hipMemsetAsync(cnt, 0, 8, s));
   HIPCHK(hipMemsetAsync(cnt + 1, 0xFF, 8, s));  // the first bad position: none
   compact_finish_kernel<<<grid_for(nv), 256, 0, s>>>(d_file, en, kh, p.a.crc, P<uint64_t>(c, B_CL_MO), nv,

@@ -1,15 +1,16 @@
-// srd_segments.h -- the arithmetic of srd_batch_append_segments_device: how a
-// segment table is judged, how an entry's segments are cut into work units,
-// what a unit's descriptor holds, and how an entry's CRC-32 is put together
-// from its units' raw CRCs.  The unit descriptor (SegUnit) and its frame are
-// also what the streaming kernel (srd_stream.hip) runs over for every caller:
-// the gather and the append describe their chunk units with it
-// (seg_chunk_unit).  Plain integer code shared by the layout / unit / combine
-// kernels (srd_segments.hip, srd_gather.hip), the streaming kernel, the host
-// glue (srd_ops.hip) and a CPU check (tests/sanitize_segments/
-// segments_check.cpp): outside HIP the qualifiers are empty.  The entry layout
-// (slots, base, the new tail, the error word) is the append's (srd_append.h) as
-// it is.
+// srd_segments.h -- the arithmetic of srd_batch_append_segments_device, and
+// the one entry model of everything that streams payload bytes: how a segment
+// table is judged, how an entry's segments are cut into work units, what a
+// unit's descriptor holds (SegUnit), what describes a batch of entries cut into
+// units (UnitArgs, read through a view: a segment table, or ranges, each its
+// own entry of one segment -- the gather's hits, the append's and the live
+// compaction's payloads), and how an entry's CRC-32 is put together from its
+// units' raw CRCs.  Plain integer code shared by the layout kernels
+// (srd_segments.hip), the unit / terms / combine kernels (srd_units.hip), the
+// streaming kernel (srd_stream.hip), the host glue (srd_ops.hip) and a CPU
+// check (tests/sanitize_segments/segments_check.cpp): outside HIP the
+// qualifiers are empty.  The entry layout (slots, base, the new tail, the error
+// word) is the append's (srd_append.h) as it is.
 //
 // Entry i's payload is the concatenation of segments first[i] .. first[i + 1);
 // segment s of it starts at offset seg_off[s] inside the entry, i.e. at file
@@ -126,17 +127,6 @@ SRD_GA_HD SegUnit seg_unit(uint64_t src_addr, uint64_t dst, uint64_t off, uint64
   seg_unit_range(dst & 15, len, k, &b0, &b1);
   return SegUnit{src_addr + b0, dst + b0, off + b1, ent, seg_unit_lf(b1 - b0, b0, len - b1, ent_units == 1)};
 }
-// Chunk k of a hit or payload of len bytes and `chunks` chunks (srd_gather.h)
-// whose destination starts at a 64-byte boundary: the range is one segment
-// that is its own entry, so the cut is the chunk cut, the below / behind counts
-// are taken against the range itself, and end is the chunk's end inside it.
-// pad: the last chunk owns the zero bytes up to the next 64-byte boundary.
-SRD_GA_HD SegUnit seg_chunk_unit(uint64_t src_addr, uint64_t dst, uint64_t len, uint64_t k, uint32_t ent, uint64_t chunks,
-                                 bool pad) {
-  SegUnit x = seg_unit(src_addr, dst, 0, len, k, ent, chunks);
-  if (pad && k + 1 == chunks) x.lf |= SEG_LF_PAD;
-  return x;
-}
 // how many zero bytes a unit owns behind its end (output offsets of hits are multiples of 64)
 SRD_GA_HD uint32_t seg_unit_pad(uint64_t dst, uint32_t lf) {
   return lf & SEG_LF_PAD ? (uint32_t)(0 - (dst + seg_lf_len(lf))) & 63u : 0u;
@@ -176,6 +166,69 @@ SRD_GA_HD bool seg_piece_vec(const SegFrame& f, uint32_t o) {
 template <class P>
 SRD_GA_HD uint32_t seg_unit_term(uint32_t raw, uint64_t ent_len, uint64_t end, P pow8) {
   return mulp(gather_xpow8(pow8, ent_len - end), raw);
+}
+
+// A batch of entries cut into units: what the unit table and the combine need
+// of it, whoever laid it out.  An entry is a run of segments; a view (below)
+// says where a segment's values are.
+struct UnitArgs {
+  uint64_t n;       // entries
+  uint64_t n_segs;  // segments (ranges: n)
+  uint64_t* eun;    // [n] an entry's unit count
+  uint64_t* off;    // [n] where its bytes go, less dst0: a multiple of 64
+  uint64_t* upre;   // [n_segs] exclusive sum of the segments' unit counts
+  // ranges: segment s is entry s, the bytes [start[s], end[s]) of file
+  const uint8_t* file;
+  const uint64_t *start, *end;
+  // a table: entry i is the segments first[i] .. first[i + 1)
+  const uint64_t* srcs;  // [2 n_src] the source table on the device: address, length
+  const srd_segment* segs;
+  const uint64_t* first;  // [n + 1]
+  uint64_t* len;          // [n] the entries' lengths
+  uint64_t* soff;         // [n_segs] a segment's offset inside its entry
+  uint64_t* sun;          // [n_segs] its unit count (upre's addends)
+  uint32_t* sent;         // [n_segs] its entry
+  uint64_t dst0;   // a multiple of 64
+  bool pad;        // an entry's last unit zeroes up to the next 64-byte boundary of the output
+  SegUnit* unit;   // [n_units] the unit table
+  uint64_t n_units;
+  uint32_t* raw;   // [n_units] a multi-unit entry's units: crc_raw, then the unit's term
+  uint32_t* crc;   // [n] an entry's CRC32
+};
+// (nothing is materialised for ranges: their unit count is eun[s], their unit
+// prefix upre[s], and the entry's first unit upre[i])
+struct RangeView {
+  static SRD_GA_HD uint64_t addr(const UnitArgs& a, uint64_t s) { return (uint64_t)(uintptr_t)a.file + a.start[s]; }
+  static SRD_GA_HD uint64_t len(const UnitArgs& a, uint64_t s) { return a.end[s] - a.start[s]; }
+  static SRD_GA_HD uint64_t soff(const UnitArgs&, uint64_t) { return 0; }
+  static SRD_GA_HD uint64_t ent(const UnitArgs&, uint64_t s) { return s; }
+  static SRD_GA_HD uint64_t first(const UnitArgs&, uint64_t i) { return i; }
+  static SRD_GA_HD uint64_t ent_len(const UnitArgs& a, uint64_t i) { return a.end[i] - a.start[i]; }
+};
+struct TableView {
+  static SRD_GA_HD uint64_t addr(const UnitArgs& a, uint64_t s) { return a.srcs[2 * a.segs[s].src] + a.segs[s].off; }
+  static SRD_GA_HD uint64_t len(const UnitArgs& a, uint64_t s) { return a.segs[s].len; }
+  static SRD_GA_HD uint64_t soff(const UnitArgs& a, uint64_t s) { return a.soff[s]; }
+  static SRD_GA_HD uint64_t ent(const UnitArgs& a, uint64_t s) { return a.sent[s]; }
+  static SRD_GA_HD uint64_t first(const UnitArgs& a, uint64_t i) { return a.first[i]; }
+  static SRD_GA_HD uint64_t ent_len(const UnitArgs& a, uint64_t i) { return a.len[i]; }
+};
+// an entry's first unit (an entry with units has a segment)
+template <class View>
+SRD_GA_HD uint64_t unit_first(const UnitArgs& a, uint64_t i) {
+  return a.upre[View::first(a, i)];
+}
+// unit u (u < n_units): piece u - upre[s] of the segment s with upre[s] <= u <
+// upre[s + 1]; of a range, that is chunk u - upre[i] of range i (srd_gather.h:
+// the destination is 64-aligned, so the cut is the chunk cut, the below /
+// behind counts are taken against the range itself, and end is the chunk's end
+// inside it)
+template <class View>
+SRD_GA_HD SegUnit unit_of(const UnitArgs& a, uint64_t u) {
+  const uint64_t s = gather_unit_hit(a.upre, a.n_segs, u), off = View::soff(a, s), ent = View::ent(a, s), k = a.eun[ent];
+  SegUnit x = seg_unit(View::addr(a, s), a.dst0 + a.off[ent] + off, off, View::len(a, s), u - a.upre[s], (uint32_t)ent, k);
+  if (a.pad && u + 1 == unit_first<View>(a, ent) + k) x.lf |= SEG_LF_PAD;
+  return x;
 }
 
 }  // namespace srd

@@ -1379,18 +1379,14 @@ class DeviceStore:
 
     # -- writes of payloads that are already on the device ----------------------------------
 
-    def _append_device(self, d_hashes, blob_ptr: int, blob_len: int, d_offs, d_lens, flags: int) -> int:
-        """srd_batch_append_device on the context stream (§10's stream rule), then
-        the reindex of its (key_hash, offset) pairs, then the tail.  Any error
-        leaves the tail and the index as they were."""
-        import torch
-        n = d_hashes.numel()
-        d_mo = torch.empty(n, dtype=torch.int64, device=self.buf.device)
+    def _append_reindex(self, call, d_hashes, d_mo) -> int:
+        """A library append call on the context stream (§10's stream rule; call()
+        returns the new tail and fills d_mo), then the reindex of its (key_hash,
+        offset) pairs, then the tail.  Any error leaves the tail and the index as
+        they were."""
         self.index._lib_after_torch()
         try:
-            new_tail = batch_append_device(blob_ptr, blob_len, d_offs.data_ptr(), d_lens.data_ptr(), d_hashes.data_ptr(), n,
-                                           flags, self._tail, self.buf.data_ptr(), self.buf.numel(), d_mo.data_ptr(),
-                                           self.ctx)
+            new_tail = call()
         except SrdError as e:
             self.index._sync_lib()  # (the inputs may be temporaries of the caller)
             if e.rc == SRD_ERR_ARG and "file_cap" in str(e):
@@ -1399,6 +1395,16 @@ class DeviceStore:
         self.index.apply(d_hashes, d_mo)  # same stream: behind the append; waits
         self._tail = new_tail
         return new_tail
+
+    def _append_device(self, d_hashes, blob_ptr: int, blob_len: int, d_offs, d_lens, flags: int) -> int:
+        """srd_batch_append_device, reindex, tail (_append_reindex)."""
+        import torch
+        n = d_hashes.numel()
+        d_mo = torch.empty(n, dtype=torch.int64, device=self.buf.device)
+        return self._append_reindex(
+            lambda: batch_append_device(blob_ptr, blob_len, d_offs.data_ptr(), d_lens.data_ptr(), d_hashes.data_ptr(), n,
+                                        flags, self._tail, self.buf.data_ptr(), self.buf.numel(), d_mo.data_ptr(),
+                                        self.ctx), d_hashes, d_mo)
 
     def batch_write_device_with_key_hashes(self, hashes, blob, offs, lens, stream_rule: bool = False) -> int:
         """batch_write_with_key_hashes(.., false) (data_store.rs:847-939) for
@@ -1469,20 +1475,11 @@ class DeviceStore:
         d_first = self.index._as_dev(np.array(first, np.uint64))
         d_hashes = self.index._as_dev(hashes)
         d_mo = torch.empty(n, dtype=torch.int64, device=dev)
-        self.index._lib_after_torch()
-        try:
-            new_tail = batch_append_segments_device([p for p, _ in srcs], [nb for _, nb in srcs], d_segs.data_ptr(),
-                                                    len(segs), d_first.data_ptr(), d_hashes.data_ptr(), n, self._tail,
-                                                    self.buf.data_ptr(), self.buf.numel(), d_mo.data_ptr(), self.ctx)
-        except SrdError as e:
-            self.index._sync_lib()  # (the inputs may be temporaries of the caller)
-            if e.rc == SRD_ERR_ARG and "file_cap" in str(e):
-                raise ValueError("the batch ends beyond the store's capacity") from e
-            raise
-        self.index.apply(d_hashes, d_mo)  # same stream: behind the append; waits
-        self._tail = new_tail
-        del keep
-        return new_tail
+        return self._append_reindex(  # (keep holds the segments until the call has returned)
+            lambda: batch_append_segments_device([p for p, _ in srcs], [nb for _, nb in srcs], d_segs.data_ptr(),
+                                                 len(segs), d_first.data_ptr(), d_hashes.data_ptr(), n, self._tail,
+                                                 self.buf.data_ptr(), self.buf.numel(), d_mo.data_ptr(), self.ctx),
+            d_hashes, d_mo)
 
     def batch_write_stream(self, keys, entries) -> int:
         """write_stream (data_store.rs:753-756) of every key: compute_hash_batch,

@@ -1,6 +1,7 @@
 // ASan/UBSan check of the payload gather's arithmetic (TEST INFRASTRUCTURE):
-// rust-simd-r-drive_amd/csrc/srd_gather.h compiled for the host, the very code
-// the layout, unit-table and combine kernels run, over the tables of srd_crc.h.
+// rust-simd-r-drive_amd/csrc/srd_gather.h (and srd_segments.h' unit cut and
+// CRC term) compiled for the host, the very code the layout, unit-table and
+// combine kernels run, over the tables of srd_crc.h.
 //   - gather_range_status: the borders of NONE / BAD_RANGE / hit, without wrap;
 //   - for seeded random batches (hits of 1 byte .. 5 chunks, None reads, bad
 //     ranges, duplicates): the units tile every hit's bytes exactly once, every
@@ -8,9 +9,12 @@
 //     the offsets -- the exclusive sum of the padded lengths -- give every
 //     payload its own 64-aligned place;
 //   - for the lengths of the GPU tests' set L and seeded random lengths up to
-//     5 chunks: the CRC combined from the per-chunk raw CRCs, serially
-//     (gather_combine) and split over the 64 lanes (gather_lane_term), equals a
-//     byte-wise CRC-32.
+//     5 chunks, cut as a range is (chunks) and as a segment at destination
+//     residue 5 is (unit 0 shorter than a chunk): the CRC combined from the
+//     per-unit raw CRCs as the combine does it -- every unit's term
+//     (seg_unit_term), XORed per lane over the units l, l + 64, ... and over
+//     the lanes, then gather_final -- equals a byte-wise CRC-32, and the
+//     lanes' shares partition the units.
 // Exit status 0 = no sanitizer report and every invariant held.
 #include <stdint.h>
 #include <stdio.h>
@@ -19,6 +23,7 @@
 #include <vector>
 
 #include "srd_gather.h"
+#include "srd_segments.h"
 
 using namespace srd;
 
@@ -115,26 +120,44 @@ static void check_batch(std::mt19937_64& rng) {
   g_units += U;
 }
 
+// the entry buf[s, s + len) at destination residue a (seg_unit_range's cut; a
+// == 0: the chunk cut of a range), combined as unit_terms_kernel and
+// unit_combine_kernel do it
 static uint64_t g_crcs = 0;
-static void check_crc(const CrcTables& t, const std::vector<uint8_t>& buf, uint64_t s, uint64_t len) {
+static void check_crc(const CrcTables& t, const std::vector<uint8_t>& buf, uint64_t s, uint64_t len, uint64_t a = 0) {
   const uint8_t* p = buf.data() + s;
   const uint32_t want = ~host_crc_raw_bytes(t, 0xFFFFFFFFu, p, len);
-  const uint64_t k = gather_chunks(len);
-  std::vector<uint32_t> raw(k);
-  for (uint64_t j = 0; j < k; j++) raw[j] = host_crc_raw_bytes(t, 0, p + j * C, gather_chunk_len(len, j));
-  EXPECT(gather_combine(raw.data(), k, len, t.pow8) == want);
-  uint32_t x = 0;
-  uint64_t cover = 0;
-  for (uint32_t l = 0; l < (uint32_t)GATHER_LANES; l++) {
-    uint64_t j0, j1;
-    gather_lane_chunks(k, l, &j0, &j1);
-    EXPECT(j0 == cover || j0 == j1);  // the lanes' shares are consecutive
-    if (j1 > j0) cover = j1;
-    x ^= gather_lane_term(raw.data(), k, l, len, t.pow8);
+  const uint64_t k = seg_unit_count(a, len);
+  if (!a) EXPECT(k == gather_chunks(len));
+  std::vector<uint32_t> term(k);
+  uint64_t at = 0;
+  for (uint64_t j = 0; j < k; j++) {
+    uint64_t b0, b1;
+    seg_unit_range(a, len, j, &b0, &b1);
+    EXPECT(b0 == at && b1 > b0 && b1 - b0 <= C && b1 == (len < (j + 1) * C - a ? len : (j + 1) * C - a));
+    if (!a) EXPECT(b0 == j * C && b1 - b0 == gather_chunk_len(len, j));
+    at = b1;
+    term[j] = seg_unit_term(host_crc_raw_bytes(t, 0, p + b0, b1 - b0), len, b1, t.pow8);
   }
-  EXPECT(cover == k);
+  EXPECT(at == len);
+  uint32_t x = 0;
+  std::vector<uint8_t> taken(k, 0);
+  for (uint64_t l = 0; l < 64; l++) {  // lane l: the units l, l + 64, ...
+    uint32_t tl = 0;
+    for (uint64_t j = l; j < k; j += 64) {
+      tl ^= term[j];
+      taken[j]++;
+    }
+    x ^= tl;
+  }
+  for (uint64_t j = 0; j < k; j++) EXPECT(taken[j] == 1);  // the lanes' shares partition 0 .. k
   EXPECT(gather_final(x, len, t.pow8) == want);
   g_crcs++;
+}
+// ... on both cuts
+static void check_crc2(const CrcTables& t, const std::vector<uint8_t>& buf, uint64_t s, uint64_t len) {
+  check_crc(t, buf, s, len);
+  check_crc(t, buf, s, len, 5);
 }
 
 int main() {
@@ -148,18 +171,18 @@ int main() {
                         C - 1, C, C + 1, 2 * C, 2 * C + 17, 3 * C + 4097};
   std::vector<uint8_t> buf(5 * C + 4096);
   for (auto& b : buf) b = (uint8_t)rng();
-  for (uint64_t len : L) check_crc(t, buf, 0, len);
+  for (uint64_t len : L) check_crc2(t, buf, 0, len);
   for (int it = 0; it < 40; it++) {
     const uint64_t len = 1 + rng() % (5 * C);
-    check_crc(t, buf, rng() % (buf.size() - len + 1), len);
+    check_crc2(t, buf, rng() % (buf.size() - len + 1), len);
   }
-  // many chunks: every lane's share longer than one chunk (C bytes each but the last)
+  // many units: lanes with one, two and three units
   {
     std::vector<uint8_t> big(131 * C + 77);
     for (auto& b : big) b = (uint8_t)rng();
-    check_crc(t, big, 0, big.size());
-    check_crc(t, big, 0, 64 * C);
-    check_crc(t, big, 0, 65 * C + 1);
+    check_crc2(t, big, 0, big.size());
+    check_crc2(t, big, 0, 64 * C);
+    check_crc2(t, big, 0, 65 * C + 1);
   }
   if (g_fail) {
     fprintf(stderr, "gather_check: %d invariant(s) failed\n", g_fail);

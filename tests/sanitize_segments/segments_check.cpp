@@ -9,7 +9,10 @@
 //     starts at a 16-byte boundary of the store;
 //   - a unit's descriptor never lets an aligned 16-byte load leave its segment;
 //   - the same for the chunk units of the gather and the append (a whole range
-//     as one segment) at every start residue, with the pad count of a last unit;
+//     as one segment: the range view) at every start residue, with the pad
+//     count of a last unit;
+//   - over seeded range batches, the range view and an explicit table of one
+//     segment per entry give the same descriptor for every unit;
 //   - the XOR of the units' terms (bitwise host CRC per unit) is the CRC-32 of
 //     the concatenation (check value 0xCBF43926 included);
 //   - the entry layout equals srd_batch_layout's for the concatenated lengths
@@ -253,9 +256,9 @@ static void check_cut() {
   }
 }
 
-// Chunk units as the gather and the append build them (seg_chunk_unit): a whole
-// range [start, end) taken as one segment whose destination starts at a 64-byte
-// boundary.  At every start residue, for lengths around 16, 4096, C and 2 C:
+// Chunk units as the gather and the append build them (unit_of<RangeView>): a
+// whole range [start, end) taken as one segment whose destination starts at a
+// 64-byte boundary (here: range 7 of 8, the others without units).  At every start residue, for lengths around 16, 4096, C and 2 C:
 // the units are the range's chunks, every aligned source vector the streaming
 // kernel's walk admits lies inside [start, end) (check_frame; the range ends at
 // its allocation's end, so the sanitizer sees a read past it), and a range's
@@ -273,9 +276,22 @@ static void check_chunk_units(std::mt19937_64& rng) {
       const uint64_t start = (uint64_t)(uintptr_t)exact + 16 + res;
       const std::vector<uint8_t> copy(exact + 16 + res, exact + 16 + res + len);
       const uint64_t chunks = gather_chunks(len), dst = 64 * (1 + rng() % 1000);
+      uint64_t r_st[8] = {0}, r_en[8] = {0}, r_un[8] = {0}, r_off[8] = {0}, r_pre[8] = {0};
+      r_st[7] = start;
+      r_en[7] = start + len;
+      r_un[7] = chunks;
+      r_off[7] = dst;
+      UnitArgs ra{};
+      ra.n = ra.n_segs = 8;
+      ra.start = r_st;
+      ra.end = r_en;
+      ra.eun = r_un;
+      ra.off = r_off;
+      ra.upre = r_pre;
       for (int pad = 0; pad < 2; pad++) {
+        ra.pad = pad;
         for (uint64_t k = 0; k < chunks; k++) {
-          const SegUnit x = seg_chunk_unit(start, dst, len, k, 7, chunks, pad);
+          const SegUnit x = unit_of<RangeView>(ra, k);
           const uint64_t cl = gather_chunk_len(len, k);
           EXPECT(x.src == start + k * C && x.dst == dst + k * C && seg_lf_len(x.lf) == cl && x.end == k * C + cl);
           EXPECT(x.ent == 7 && seg_lf_single(x.lf) == (chunks == 1) && (x.dst & 15) == 0);
@@ -289,6 +305,85 @@ static void check_chunk_units(std::mt19937_64& rng) {
       }
       free(exact);
     }
+  }
+}
+
+// Range batches (the generator of gather_check.cpp's check_batch: hits of 1
+// byte .. 5 chunks, None reads, bad ranges, duplicates) as the gather lays them
+// out, with a 64-aligned dst0, with and without pad: the range view and an
+// explicit table of one segment per entry (a range without units: an empty
+// segment) give the same descriptor for every unit.  Nothing is dereferenced.
+static uint64_t g_view_units = 0;
+static void check_views(std::mt19937_64& rng) {
+  const uint64_t F = 40 * C;
+  const uint64_t n = 1 + rng() % 200;
+  std::vector<uint64_t> st(n), en(n), len(n), chk(n), off(n + 1), cpre(n + 1), zero(n, 0), first(n + 1);
+  std::vector<uint32_t> sent(n);
+  std::vector<srd_segment> segs(n);
+  static const uint8_t file[64] = {0};  // (the ranges' base address only)
+  uint64_t so = 0, sc = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint32_t kind = rng() % 10;
+    uint64_t l;
+    switch (rng() % 5) {
+      case 0: l = 1 + rng() % 200; break;
+      case 1: l = 1 + rng() % (5 * C); break;
+      case 2: l = C * (1 + rng() % 5); break;
+      case 3: l = C * (1 + rng() % 4) + (rng() % 2 ? 1 : C - 1); break;
+      default: l = 1 + rng() % 9000; break;
+    }
+    st[i] = (rng() % (F - 20 - l)) & (rng() % 4 ? ~63ull : ~0ull);
+    en[i] = st[i] + l;
+    if (kind == 0) en[i] = st[i];                       // a None read
+    if (kind == 1) std::swap(st[i], en[i]);             // start > end
+    if (kind == 2) en[i] = F - rng() % 20;              // metadata past the end
+    if (kind == 3 && i) { st[i] = st[i - 1]; en[i] = en[i - 1]; }  // a duplicate
+    len[i] = gather_range_status(st[i], en[i], F) == SRD_GATHER_OK ? en[i] - st[i] : 0;
+    chk[i] = gather_chunks(len[i]);
+    off[i] = so;
+    cpre[i] = sc;
+    so += gather_pad64(len[i]);
+    sc += chk[i];
+    segs[i] = srd_segment{};
+    segs[i].off = len[i] ? st[i] : 0;
+    segs[i].len = len[i];
+    sent[i] = (uint32_t)i;
+    first[i] = i;
+  }
+  off[n] = so;
+  cpre[n] = sc;
+  first[n] = n;
+  const uint64_t srcs[2] = {(uint64_t)(uintptr_t)file, F};
+  for (int pad = 0; pad < 2; pad++) {
+    UnitArgs r{};
+    r.n = r.n_segs = n;
+    r.eun = chk.data();
+    r.off = off.data();
+    r.upre = cpre.data();
+    r.dst0 = 64 * (rng() % 100000);
+    r.pad = pad;
+    r.n_units = sc;
+    UnitArgs tb = r;
+    r.file = file;
+    r.start = st.data();
+    r.end = en.data();
+    tb.srcs = srcs;
+    tb.segs = segs.data();
+    tb.first = first.data();
+    tb.len = len.data();
+    tb.soff = zero.data();
+    tb.sun = chk.data();
+    tb.sent = sent.data();
+    for (uint64_t u = 0; u < sc; u++) {
+      const SegUnit x = unit_of<RangeView>(r, u), y = unit_of<TableView>(tb, u);
+      EXPECT(x.src == y.src && x.dst == y.dst && x.end == y.end && x.ent == y.ent && x.lf == y.lf);
+      EXPECT(x.ent < n && RangeView::ent_len(r, x.ent) == TableView::ent_len(tb, x.ent));
+      EXPECT(unit_first<RangeView>(r, x.ent) == unit_first<TableView>(tb, x.ent));
+      const uint64_t k = u - cpre[x.ent];  // the bits of a chunk unit
+      EXPECT(x.src == (uint64_t)(uintptr_t)file + st[x.ent] + k * C && x.dst == r.dst0 + off[x.ent] + k * C);
+      EXPECT(seg_lf_len(x.lf) == gather_chunk_len(len[x.ent], k) && !(x.lf & SEG_LF_PAD) == !(pad && k + 1 == chk[x.ent]));
+    }
+    g_view_units += sc;
   }
 }
 
@@ -390,13 +485,14 @@ int main() {
     for (int it = 0; it < 3; it++) check_tables(t, rng, (rng() % 5000) * 64 + res, src);
   for (uint64_t res = 0; res < 64; res++) check_tables(t, rng, res, src);  // (a store of less than one line)
   check_chunk_units(rng);
+  for (int it = 0; it < 100; it++) check_views(rng);
   check_refusals();
   if (g_fail) {
     fprintf(stderr, "segments_check: %d invariant(s) failed\n", g_fail);
     return 1;
   }
-  printf("segments_check ok: chunk %llu, %llu entries, %llu segments, %llu units, %llu chunk units\n", (unsigned long long)C,
-         (unsigned long long)g_entries, (unsigned long long)g_segs, (unsigned long long)g_units,
-         (unsigned long long)g_chunk_units);
+  printf("segments_check ok: chunk %llu, %llu entries, %llu segments, %llu units, %llu chunk units, %llu units under both views\n",
+         (unsigned long long)C, (unsigned long long)g_entries, (unsigned long long)g_segs, (unsigned long long)g_units,
+         (unsigned long long)g_chunk_units, (unsigned long long)g_view_units);
   return 0;
 }

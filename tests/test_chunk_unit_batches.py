@@ -1,9 +1,9 @@
 """The batches tests/test_gpu_chunk_units.py runs, and what they must cover.
 
-A host restatement of the chunk units of srd_gather.h / srd_gather.hip -- how a
+A host restatement of the chunk units of srd_gather.h / srd_units.hip -- how a
 batch's hits are cut into units, which wave of stream_copy_crc_kernel's grid
-walks which units, and how payload_combine_kernel splits a hit's chunks over
-its 64 lanes -- plus the seeded generators of the batches.  The tests here need
+walks which units, and how unit_combine_kernel splits a hit's units over its
+64 lanes -- plus the seeded generators of the batches.  The tests here need
 no GPU: they assert that the generated batches meet the coverage conditions
 for every grid size the GPU test may meet (W = 16 waves x 64, 256 and 304
 CUs), so that on the device those conditions are facts, not luck."""
@@ -16,10 +16,10 @@ import srd_amd as S
 
 CH = S.GATHER_CHUNK
 TILE = 4096          # stream_copy_crc_kernel's block (srd_stream.hip)
-GATHER_LANES = 64    # srd_gather.h
+COMBINE_LANES = 64   # unit_combine_kernel's wave (srd_units.hip)
 # SCAN_WAVES_V2 (srd_kernels.hip): the waves of one stream_copy_crc_kernel block.  The grid is
 # min(ceil(units / SCAN_WAVES_V2), c->scan_blocks) blocks, scan_blocks = the CU count (launch_stream,
-# srd_ops.hip, for srd_payload_gather_device and append_commit alike), so a batch of more than W = 16 x CUs units gives
+# srd_ops.hip, for srd_payload_gather_device and plan_commit alike), so a batch of more than W = 16 x CUs units gives
 # wave w the units w, w + W, w + 2 W, ...
 WAVES_PER_BLOCK = 16
 GRIDS = [WAVES_PER_BLOCK * cus for cus in (64, 256, 304)]
@@ -32,46 +32,57 @@ COMBINE_LENGTHS = [(k - 1) * CH + COMBINE_R[i % len(COMBINE_R)] for i, k in enum
 
 
 def lane_split(k):
-    """gather_lane_chunks: (s, [(j0, j1) per lane]) -- lane l folds the chunks [l s, min(k, (l + 1) s))."""
-    s = (k + GATHER_LANES - 1) // GATHER_LANES
-    return s, [(min(s * l, k), min(s * l + s, k)) for l in range(GATHER_LANES)]
+    """unit_combine_kernel's split of an entry's k units over the 64 lanes of its wave: lane l XORs the terms of
+    the units l, l + 64, l + 128, ...  Returns the list of units per lane."""
+    return [list(range(l, k, COMBINE_LANES)) for l in range(COMBINE_LANES)]
 
 
 def last_lane(k):
-    """The last lane that holds a chunk."""
-    return max(l for l, (a, b) in enumerate(lane_split(k)[1]) if a < b)
+    """The last lane that holds a unit."""
+    return max(l for l, us in enumerate(lane_split(k)) if us)
 
 
 def combine_flip_positions(n):
-    """The byte positions test A1 flips in a hit of n bytes: byte 0, the last byte, the first byte of lane 1's
-    first chunk, and a byte in the last non-empty lane's first chunk."""
+    """The byte positions test A1 flips in a hit of n bytes (more than 64 units): byte 0, the last byte, the first
+    byte of unit 1 (lane 1), byte 7 of unit 63 (the last lane's first unit), byte 7 of unit 64 (lane 0's second
+    round) and, for 129 units or more, byte 7 of unit 128 (lane 0's third round) -- unless that unit is shorter
+    than 8 bytes: it is the hit's last unit then, and the last byte already lies in it."""
     k = (n + CH - 1) // CH
-    s, seg = lane_split(k)
-    pos = [0, n - 1, s * CH, seg[last_lane(k)][0] * CH + 7]
-    assert len(set(pos)) == 4 and all(0 <= p < n for p in pos)
+    split = lane_split(k)
+    assert k > 64 and split[1][0] == 1 and split[last_lane(k)][0] == 63 and split[0][1] == 64
+    pos = [0, n - 1, CH, 63 * CH + 7, 64 * CH + 7]
+    if k >= 129:
+        assert split[0][2] == 128
+        if 128 * CH + 7 < n:
+            pos.append(128 * CH + 7)
+        assert any(p // CH == 128 for p in pos)
+    assert len(set(pos)) == len(pos) and all(0 <= p < n for p in pos)
     return pos
 
 
 def test_combine_lengths_change_the_split():
     assert [(n + CH - 1) // CH for n in COMBINE_LENGTHS] == COMBINE_K and sum(COMBINE_K) == 645
     assert set((n - 1) % CH + 1 for n in COMBINE_LENGTHS) == set(COMBINE_R)
-    full = lambda k: [l for l, (a, b) in enumerate(lane_split(k)[1]) if b - a == lane_split(k)[0]]
-    used = lambda k: [l for l, (a, b) in enumerate(lane_split(k)[1]) if b > a]
-    assert lane_split(63)[0] == 1 and used(63) == list(range(63))
-    assert lane_split(64)[0] == 1 and full(64) == list(range(64))           # the last k with s = 1
-    s, seg = lane_split(65)
-    assert s == 2 and used(65) == list(range(33)) and seg[32] == (64, 65)   # lanes 33-63 empty, lane 32 holds one chunk
-    assert lane_split(66)[0] == 2 and full(66) == used(66) == list(range(33))
-    assert lane_split(128)[0] == 2 and full(128) == list(range(64))
-    s, seg = lane_split(129)
-    assert s == 3 and full(129) == used(129) == list(range(43)) and seg[42] == (126, 129)
-    s, seg = lane_split(130)
-    assert s == 3 and used(130) == list(range(44)) and seg[43] == (129, 130)  # lane 43 holds one chunk
-    for k in COMBINE_K:  # the segments are a partition of the chunks
-        assert [j for a, b in lane_split(k)[1] for j in range(a, b)] == list(range(k))
-    # a flipped byte of lane 1's and of the last lane's share lies in a segment of several chunks for k = 129
-    assert combine_flip_positions(COMBINE_LENGTHS[5]) == [0, 128 * CH, 3 * CH, 126 * CH + 7]
-    assert combine_flip_positions(COMBINE_LENGTHS[2]) == [0, 64 * CH + 4096, 2 * CH, 64 * CH + 7]
+    rounds = lambda k: sorted(set(len(us) for us in lane_split(k)))   # the lanes' unit counts
+    used = lambda k: [l for l, us in enumerate(lane_split(k)) if us]
+    assert rounds(63) == [0, 1] and used(63) == list(range(63)) and last_lane(63) == 62   # lane 63 empty
+    assert rounds(64) == [1] and last_lane(64) == 63                        # the last k of one round
+    assert rounds(65) == [1, 2] and lane_split(65)[0] == [0, 64]            # lane 0 alone has a second round
+    assert all(us == [l] for l, us in enumerate(lane_split(65)) if l)
+    assert rounds(66) == [1, 2] and [l for l, us in enumerate(lane_split(66)) if len(us) == 2] == [0, 1]
+    assert rounds(128) == [2] and lane_split(128)[63] == [63, 127]          # the last k of two rounds
+    assert rounds(129) == [2, 3] and lane_split(129)[0] == [0, 64, 128]     # lane 0 alone has a third round
+    assert all(us == [l, l + 64] for l, us in enumerate(lane_split(129)) if l)
+    assert rounds(130) == [2, 3] and lane_split(130)[1] == [1, 65, 129] and lane_split(130)[2] == [2, 66]
+    for k in COMBINE_K:  # the lanes' shares are a partition of the units
+        assert sorted(j for us in lane_split(k) for j in us) == list(range(k))
+        assert all(j % COMBINE_LANES == l for l, us in enumerate(lane_split(k)) for j in us)
+        assert used(k) == list(range(min(k, COMBINE_LANES)))
+    # the flipped bytes of the k = 129 and the k = 65 hit: each in a unit of another lane or round (the k = 129
+    # hit ends one byte into unit 128, so its last byte is the position in lane 0's third round)
+    assert combine_flip_positions(COMBINE_LENGTHS[5]) == [0, 128 * CH, CH, 63 * CH + 7, 64 * CH + 7]
+    assert combine_flip_positions(COMBINE_LENGTHS[2]) == [0, 64 * CH + 4096, CH, 63 * CH + 7, 64 * CH + 7]
+    assert combine_flip_positions(COMBINE_LENGTHS[6]) == [0, 129 * CH + 16, CH, 63 * CH + 7, 64 * CH + 7, 128 * CH + 7]
 
 
 # -- part B: more units than waves -----------------------------------------------------------------

@@ -63,10 +63,11 @@ def test_python_interface_names():
 def test_gather_arithmetic_sanitized():
     """csrc/srd_gather.h as a plain executable under ASan + UBSan (nothing is
     loaded into Python): the units tile every hit exactly once and unit -> hit
-    inverts; the CRC combined from per-chunk raw CRCs (serially and split over
-    the combine's 64 lanes) equals a byte-wise CRC-32 for the GPU tests' length
-    set and seeded random lengths up to 5 chunks; the offsets are the exclusive
-    sum of the padded lengths; the range rule's borders."""
+    inverts; the CRC combined from per-unit raw CRCs (every unit's term, XORed
+    as the combine's 64 lanes stride over the units, for the chunk cut and for
+    a cut at destination residue 5) equals a byte-wise CRC-32 for the GPU
+    tests' length set and seeded random lengths up to 5 chunks; the offsets are
+    the exclusive sum of the padded lengths; the range rule's borders."""
     d = os.path.join(ROOT, "tests", "sanitize_gather")
     subprocess.check_call(["make", "-s", "-C", d])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")

@@ -1,11 +1,12 @@
 """Chunk units at many chunks per hit and many units per wave: the shapes of
-payload_units_kernel / stream_copy_crc_kernel / payload_combine_kernel that the
+units_kernel / stream_copy_crc_kernel / unit_terms_kernel + unit_combine_kernel that the
 length lists of test_gpu_gather.py, test_gpu_append.py and
 test_gpu_compact_live.py do not reach, through all three callers
 (srd_payload_gather_device, srd_batch_append_device, DeviceStore.compact).
 
-A. Hits of 63..130 chunks: the combine's lane split at s = ceil(k / 64) = 1, 2
-   and 3, with full, ragged and empty lanes.
+A. Hits of 63..130 chunks: the combine's lanes stride over a hit's units by
+   64, in 1, 2 and 3 rounds, with an empty lane, full rounds and rounds that
+   only the first lanes take.
 B. Batches of at least 2.5 W units, W = the grid's waves: every wave walks
    from one unit to the next, over every ordered pair of block counts (1, 2,
    3, 5, 16), of source alignments, and across the end of a multi-chunk hit.
@@ -120,10 +121,9 @@ def combine_appended(combine):
 
 def test_combine_gather(ctx, combine):
     names, pays, crcs = combine
-    s65, seg65 = U.lane_split(65)
-    s129, seg129 = U.lane_split(129)
-    assert s65 == 2 and seg65[32] == (64, 65) and all(a == b for a, b in seg65[33:])
-    assert s129 == 3 and seg129[42] == (126, 129) and all(a == b for a, b in seg129[43:])
+    seg65, seg129 = U.lane_split(65), U.lane_split(129)
+    assert seg65[0] == [0, 64] and all(us == [l] for l, us in enumerate(seg65) if l)
+    assert seg129[0] == [0, 64, 128] and all(us == [l, l + 64] for l, us in enumerate(seg129) if l)
     buf = bytearray()
     O.write_entries(buf, 0, [(kh(k), p) for k, p in zip(names, pays)])
     f = bytes(buf)
@@ -144,8 +144,9 @@ def test_combine_gather(ctx, combine):
     # one flipped byte per position in the k = 65 and the k = 129 hit: reported with the flipped bytes' CRC
     victims = [U.COMBINE_K.index(65), U.COMBINE_K.index(129)]
     pos = {i: U.combine_flip_positions(len(pays[i])) for i in victims}
+    assert len(pos[victims[0]]) == len(pos[victims[1]]) == 5
     cur = f
-    for q in range(4):
+    for q in range(5):
         g2 = bytearray(f)
         for i in victims:
             g2[st[i] + pos[i][q]] ^= 0xFF
@@ -159,6 +160,33 @@ def test_combine_gather(ctx, combine):
         assert list(r.status) == [S.GATHER_BAD_CRC if i in victims else S.GATHER_OK for i in range(n)], q
         assert [int(x) for x in r.crc] == [O.crc32(w) for w in want], q
         G.check_packed(r.out, r.offs, r.total, want)  # the copied bytes are the flipped bytes
+
+
+def test_combine_three_range_callers(ctx, combine):
+    """The same seven ranges through the three range callers of the one combine: gathered, verified only, and
+    copied into an empty store (batch_copy: the append under the stream rule).  Each reports the oracle's CRC-32
+    per entry; the copied store is the oracle writer's."""
+    names, pays, crcs = combine
+    entries = [(kh(k), p) for k, p in zip(names, pays)]
+    buf = bytearray()
+    O.write_entries(buf, 0, entries)
+    f = bytes(buf)
+    rg = G.host_ranges(f)
+    st, en = [rg[h][0] for h, _ in entries], [rg[h][1] for h, _ in entries]
+    assert [b - a for a, b in zip(st, en)] == U.COMBINE_LENGTHS
+    src = K.open_store(ctx, f)
+    for flags in (0, S.GATHER_VERIFY_ONLY):
+        out = sentinel_out() if flags else None
+        g = G.Raw(ctx, src.buf.data_ptr(), len(f), st, en, flags, **({"out": out, "cap": out.numel()} if flags else {}))
+        assert g.rc == 0 and list(g.status) == [S.GATHER_OK] * len(names), flags
+        assert [int(x) for x in g.crc] == crcs, flags
+    dst = S.DeviceStore.create(len(f) + 4096, ctx)
+    assert src.batch_copy(names, dst) == len(f)
+    got = dst.bytes()
+    assert got == f  # (the oracle wrote the same entries to an empty store)
+    # an entry's metadata follows its payload: key hash, prev offset, checksum
+    assert [int.from_bytes(got[m + 16: m + 20], "little") for m in en] == crcs
+    assert dst.batch_read(names) == pays
 
 
 @pytest.mark.parametrize("flags", [0, S.APPEND_STREAM_RULE])
@@ -201,12 +229,12 @@ def test_combine_compact(ctx, combine):
     assert st.tail == len(want) and st.len() == 7
     assert st.bytes() == want
     assert st.batch_read(names + [b"gone"]) == pays + [None]
-    # one byte of a high lane's chunk of the k = 129 payload, flipped in the source of a fresh session
+    # one byte of the last lane's first unit of the k = 129 payload, flipped in the source of a fresh session
     st = K.open_store(ctx, f)
     a, _e, mo, _k = next(t for t in its if t[3] == kh(b"k-129"))
     lane = U.last_lane(129)
-    q = a + U.lane_split(129)[1][lane][0] * CH + 7
-    assert lane == 42 and q < mo
+    q = a + U.lane_split(129)[lane][0] * CH + 7
+    assert lane == 63 and q < mo
     st.buf[q] ^= 0x10
     flipped = bytearray(f)
     flipped[q] ^= 0x10
