@@ -750,7 +750,7 @@ int srd_batch_append_device(srd_ctx *ctx, const uint8_t *d_payloads, uint64_t pa
  * (later work on `stream` sees the store and d_meta_off_out).  The workspace
  * comes from the context (srd_ctx_device_bytes counts it). */
 typedef struct {
-  uint32_t src;       /* index into the call's source table */
+  uint32_t src;       /* index into the call's source table (srd_payload_scatter_device: its DESTINATION table) */
   uint32_t reserved;  /* 0 */
   uint64_t off, len;  /* the bytes sources[src][off .. off + len); len may be 0 */
 } srd_segment;        /* 24 bytes, no padding */
@@ -762,6 +762,76 @@ int srd_batch_append_segments_device(srd_ctx *ctx, const uint8_t *const *src_ptr
                                      uint64_t tail, uint8_t *d_file, uint64_t file_cap,
                                      uint64_t *new_tail, uint64_t *d_meta_off_out /* n */,
                                      void *stream);
+
+/* ---- verified payloads read into a sequence of device segments ----
+ *   srd_payload_scatter_device <- EntryStream, a Read over an EntryHandle that
+ *                                 fills the caller's buffers piece by piece
+ *                                 (src/storage_engine/entry_stream.rs:44-92),
+ *                                 with EntryHandle::is_valid_checksum
+ *                                 (simd-r-drive-entry-handle/src/entry_handle.rs:260-275),
+ *                                 for a whole batch of ranges
+ * The read-side mirror of srd_batch_append_segments_device: no packed buffer,
+ * every payload goes straight to where the caller wants its pieces.
+ * d_start / d_end are srd_payload_gather_device's ranges, word for word: n
+ * payload ranges [start, end), end the entry's metadata offset, the stored
+ * checksum the little-endian u32 at d_file[end + 16 .. end + 20); any start
+ * alignment is accepted; start == end is a read's None; a range that does not
+ * lie inside the file with its metadata is SRD_GATHER_BAD_RANGE.
+ * dst_ptrs / dst_lens are HOST arrays of n_dst writable device ranges
+ * [dst_ptrs[k], dst_ptrs[k] + dst_lens[k]): the call's destination table, as
+ * src_ptrs / src_lens are the segment append's source table.  It is uploaded
+ * before the call's one wait: the host arrays are the caller's again on
+ * return.  Table ranges may overlap each other.
+ * d_segs / d_seg_first (device) are the segment append's arrays and the same
+ * srd_segment, src being the index into the DESTINATION table: query i's
+ * payload is delivered in order into the segments d_segs[first[i] .. first[i +
+ * 1]), segment s receiving the payload bytes [soff_s, soff_s + len_s), soff_s
+ * the sum of the lengths before it in the query.  A segment may be empty;
+ * several segments may point into one table range (one arena).  Two segments
+ * of one call that name the same destination byte are not detected: that byte
+ * ends as one of the bytes written to it; statuses and CRCs are still right.
+ * d_status[i]:
+ *   SRD_GATHER_NONE       start == end: the query's segments are ignored,
+ *                         nothing is written;
+ *   SRD_GATHER_BAD_RANGE  as the gather: nothing read, nothing written;
+ *   SRD_GATHER_OK         delivered, crc32(payload) == the stored checksum;
+ *   SRD_GATHER_BAD_CRC    delivered faithfully, the checksum differs;
+ *   SRD_SCATTER_BAD_LENGTH  the segments' lengths do not sum to end - start:
+ *                         nothing of the entry is read, none of its
+ *                         destinations is written.
+ * The range decides before the length does.  d_crc_computed[i] (nullable) =
+ * crc32(payload i), 0 for NONE / BAD_RANGE / BAD_LENGTH.
+ * No byte outside the named destination bytes of OK / BAD_CRC queries is
+ * written: no padding, no zero fill; the bytes between, below and behind
+ * segments are left alone, the other 15 bytes of a 16-byte vector that holds a
+ * segment's head or tail included (whole 16-byte vectors are stored wherever a
+ * vector lies inside one segment, at any source and destination alignment).
+ * Of a payload nothing outside [start, end) is read, plus its 4 checksum bytes.
+ * SRD_ERR_ARG, nothing written to any destination, d_status or d_crc_computed
+ * (the first refused query in batch order decides the message):
+ *   a malformed segment -- src >= n_dst, reserved != 0, a range not inside its
+ *     table range (judged without wrap): never dereferenced, and it decides
+ *     whatever the query's status would be;
+ *   a malformed d_seg_first: first[0] != 0, a decreasing pair, first[n] !=
+ *     n_segs;
+ *   flags != 0; n >= 2^31; n_segs >= 2^31; n_dst >= 2^32; 2^32 or more work
+ *     units (pieces of at most SRD_GATHER_CHUNK bytes of one segment);
+ *   a table range of length > 0 with a NULL pointer, or one that meets d_file[0
+ *     .. srd_padded_size(file_len)) -- checked on the host before anything runs.
+ * n == 0 runs nothing.
+ * Ordered on `stream`; waits once, for the error word, the unit total and the
+ * multi-unit count, and returns with the copy and the finish enqueued: later
+ * work on `stream` sees the destinations and both output arrays; d_segs and
+ * d_seg_first stay alive as for any stream work.  The workspace comes from the
+ * context (srd_ctx_device_bytes counts it). */
+#define SRD_SCATTER_BAD_LENGTH 4u /* d_status: the segments' lengths do not sum to end - start */
+int srd_payload_scatter_device(srd_ctx *ctx, const uint8_t *d_file, uint64_t file_len,
+                               const uint64_t *d_start, const uint64_t *d_end, uint64_t n,
+                               uint8_t *const *dst_ptrs, const uint64_t *dst_lens, uint64_t n_dst,
+                               const srd_segment *d_segs, uint64_t n_segs,
+                               const uint64_t *d_seg_first /* n + 1 */, uint32_t flags /* 0 */,
+                               uint8_t *d_status /* n */, uint32_t *d_crc_computed /* n, nullable */,
+                               void *stream);
 
 /* ---- a live session compacted on the device, its index carried over ----
  *   srd_compact_live_device <- DataStore::compact (data_store.rs:706-749) over

@@ -15,8 +15,10 @@
 //                             CRC is combined with (a CPU check uses it too)
 //     srd_append.h            the device append's range rule, layout and refusals (a CPU check uses it too)
 //     srd_segments.h          the segment append's table rule and unit cut; for every caller the unit descriptor, the
-//                             batch cut into units (UnitArgs) under its two views, a unit's CRC term and the frame
+//                             batch cut into units (UnitArgs) under its three views, a unit's CRC term and the frame
 //                             of the streaming kernel (a CPU check uses it too)
+//     srd_scatter.h           the scatter read's entry walk: segments against the destination table, the length
+//                             comparison, unit counts at the destination's residue (a CPU check uses it too)
 //     srd_stream.hip          the streaming copy + CRC kernel, one wave per unit descriptor, for any source /
 //                             destination alignment: the gather's, both appends' and the live compaction's
 //                             (uses the writer's helpers)
@@ -27,6 +29,7 @@
 //                             append's) and finish around the unit kernels
 //     srd_segments.hip        entries made of device segments appended to a store: layout (around the unit kernels
 //                             and the append's finish)
+//     srd_scatter.hip         verified payloads read into device segments: layout and finish around the unit kernels
 //     srd_table.h             the lookup table's rule: slot states, probe, claim, size arithmetic (the host entries
 //                             and a CPU check use it too)
 //     srd_index.hip           lookup table build and reads, iterator, compaction
@@ -43,7 +46,8 @@
 //     srd_host_input.hip      staging, pinned host results, host-pointer entries
 //     srd_multi.hip           multi-GPU open
 //     srd_ops.hip             probe, batch digests, synth, writer, table / reads / maintenance, iterator,
-//                             compaction, payload gather, device append, segment append, live compaction
+//                             compaction, payload gather and scatter, device append, segment append, live
+//                             compaction
 //   this file               error / build-info entries, stamps read-outs, host self-test
 //
 // Glue scans/compactions use hipCUB (library primitives, like calling
@@ -74,11 +78,13 @@
 #include "srd_gather.h"
 #include "srd_append.h"
 #include "srd_segments.h"
+#include "srd_scatter.h"
 #include "srd_stream.hip"
 #include "srd_units.hip"
 #include "srd_gather.hip"
 #include "srd_append.hip"
 #include "srd_segments.hip"
+#include "srd_scatter.hip"
 #include "srd_table.h"
 #include "srd_index.hip"
 #include "srd_index_live.hip"

@@ -1,7 +1,8 @@
 // srd_ops.hip -- host launch code of the remaining kernel families (included
 // by srd_api.hip): stream probe, batch digests, synth, batch writer, device
 // lookup table, batched reads and the table's maintenance, iterator and
-// compaction, payload gather, device append, segment append, live compaction.
+// compaction, payload gather and scatter, device append, segment append, live
+// compaction.
 
 // A device allocation / an event that lasts for one call, released on every return path
 // (no workspace buffer: as large as the caller's input, the context would keep and report it)
@@ -683,10 +684,12 @@ static int stream_units_as(Ctx* c, hipStream_t s, UnitArgs a, uint64_t units, ui
   }
   return 0;
 }
-// (a batch with a segment table is read through it, any other as ranges)
+// (a batch with a segment table is read through it -- ranges of a file
+// delivered into a table: the scatter -- any other as ranges)
 static int stream_units(Ctx* c, hipStream_t s, const UnitArgs& a, uint64_t units, uint64_t n_multi, uint8_t* out,
                         uint32_t* nz) {
-  return a.segs ? stream_units_as<TableView>(c, s, a, units, n_multi, out, nz)
+  return a.segs ? a.start ? stream_units_as<ScatterView>(c, s, a, units, n_multi, out, nz)
+                          : stream_units_as<TableView>(c, s, a, units, n_multi, out, nz)
                 : stream_units_as<RangeView>(c, s, a, units, n_multi, out, nz);
 }
 
@@ -764,6 +767,103 @@ extern "C" int srd_payload_gather_device(srd_ctx* c, const uint8_t* d_file, uint
   if (!a.layout_only && units) TRY(stream_units(c, s, a, units, n_multi, d_out, nullptr));
   payload_finish_kernel<<<grid_for(n + 1), 256, 0, s>>>(a);
   LAUNCHED(s, "payload_finish_kernel");
+  return 0;
+}
+
+// Verified payloads into the caller's segments (srd_scatter.hip): the gather's
+// sequence with the segment append's table -- the table's upload, the layout,
+// one wait for the error word, the unit total and the multi-unit count, then
+// the unit table, the streaming kernel, the combine and the finish enqueued on
+// the stream.  The streaming kernel's out is the 16-byte boundary at or below
+// the lowest destination: every unit's destination is an offset from it.
+extern "C" int srd_payload_scatter_device(srd_ctx* c, const uint8_t* d_file, uint64_t flen, const uint64_t* d_start,
+                                          const uint64_t* d_end, uint64_t n, uint8_t* const* dst_ptrs,
+                                          const uint64_t* dst_lens, uint64_t n_dst, const srd_segment* d_segs,
+                                          uint64_t n_segs, const uint64_t* d_seg_first, uint32_t flags, uint8_t* d_status,
+                                          uint32_t* d_crc_computed, void* stream) {
+  if (!c || (n_dst && (!dst_ptrs || !dst_lens)) || (n_segs && !d_segs) ||
+      (n && (!d_start || !d_end || !d_seg_first || !d_status || (flen && !d_file)))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  if (flags) { set_err("bad argument: flags must be 0"); return SRD_ERR_ARG; }
+  if (n >= (1ull << 31)) { set_err("too many queries in one batch"); return SRD_ERR_ARG; }
+  if (n_segs >= (1ull << 31)) { set_err("too many segments in one batch"); return SRD_ERR_ARG; }
+  if (n_dst >= (1ull << 32)) { set_err("too many destinations in one batch"); return SRD_ERR_ARG; }
+  if (!n) return 0;
+  std::vector<uint64_t> tab(2 * n_dst);
+  uint64_t base = ~0ull;  // the lowest destination address
+  const uintptr_t f0 = (uintptr_t)d_file, f1 = f0 + srd_padded_size(flen);
+  for (uint64_t k = 0; k < n_dst; k++) {
+    const uintptr_t p0 = (uintptr_t)dst_ptrs[k], len = (uintptr_t)dst_lens[k];
+    if (len && !p0) { set_err("bad argument: destination " + std::to_string(k) + " is NULL"); return SRD_ERR_ARG; }
+    // no destination may lie in what the store's kernels read (p0 + len may not be formed: it could wrap)
+    if (len && d_file && p0 < f1 && (f0 <= p0 || f0 - p0 < len)) {
+      set_err("destination " + std::to_string(k) + " overlaps the store");
+      return SRD_ERR_ARG;
+    }
+    if (len) base = std::min<uint64_t>(base, p0);
+    tab[2 * k] = p0;
+    tab[2 * k + 1] = len;
+  }
+  base &= ~15ull;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream_of(c, stream);
+  TRY(ensure(c, B_GA_ST, n));
+  TRY(ensure(c, B_GA_CHK, n * 8));
+  TRY(ensure(c, B_GA_CRC, n * 4));
+  TRY(ensure(c, B_GA_CNT, 64));
+  TRY(ensure(c, B_SG_SRC, tab.size() * 8));
+  TRY(ensure(c, B_SG_OFF, n_segs * 8));
+  TRY(ensure(c, B_SG_UN, n_segs * 8));
+  TRY(ensure(c, B_SG_UPRE, n_segs * 8));
+  TRY(ensure(c, B_SG_ENT, n_segs * 4));
+  TRY(ensure_scan(c, (const uint64_t*)nullptr, (uint64_t*)nullptr, std::max<uint64_t>(n_segs, 1)));
+  ScatterArgs a{};
+  a.n = n;
+  a.n_segs = n_segs;
+  a.eun = P<uint64_t>(c, B_GA_CHK);
+  a.upre = P<uint64_t>(c, B_SG_UPRE);
+  a.file = d_file;
+  a.start = d_start;
+  a.end = d_end;
+  a.srcs = P<uint64_t>(c, B_SG_SRC);
+  a.segs = d_segs;
+  a.first = d_seg_first;
+  a.soff = P<uint64_t>(c, B_SG_OFF);
+  a.sun = P<uint64_t>(c, B_SG_UN);
+  a.sent = P<uint32_t>(c, B_SG_ENT);
+  a.dst0 = base;
+  a.crc = P<uint32_t>(c, B_GA_CRC);
+  a.flen = flen;
+  a.n_dst = n_dst;
+  a.st = P<uint8_t>(c, B_GA_ST);
+  a.cnt = P<unsigned long long>(c, B_GA_CNT);
+  a.o_status = d_status;
+  a.o_crc = d_crc_computed;
+  // (the table is the caller's for the call: the wait below comes before the return)
+  if (!tab.empty()) HIPCHK(hipMemcpyAsync(P<void>(c, B_SG_SRC), tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(a.cnt, 0, 8, s));
+  HIPCHK(hipMemsetAsync(a.cnt + 1, 0xFF, 8, s));  // the error word: none
+  if (n_segs) HIPCHK(hipMemsetAsync(a.sun, 0, n_segs * 8, s));  // (a malformed d_seg_first leaves segments unvisited)
+  scatter_layout_kernel<<<grid_for(n), 256, 0, s>>>(a);
+  LAUNCHED(s, "scatter_layout_kernel");
+  // everything the host decides on, on one wait
+  uint64_t units = 0;
+  struct { unsigned long long n_multi, err; } h{};
+  if (n_segs) TRY(scan_sum_total(c, (const uint64_t*)a.sun, a.upre, n_segs, s, &units, SmallRead{a.cnt, &h, sizeof h}));
+  else TRY(read_small(c, s, {SmallRead{a.cnt, &h, sizeof h}}));  // (no query has a segment: NONE, BAD_RANGE or BAD_LENGTH)
+  if (h.err != ~0ull) {
+    const std::string i = std::to_string(h.err >> 8);
+    set_err(append_err_status(h.err) == SEG_BAD_SEGMENT
+                ? "query " + i + " has a malformed segment (src, reserved, or a range outside its destination)"
+                : "d_seg_first is malformed at query " + i);
+    return SRD_ERR_ARG;
+  }
+  if (units >= (1ull << 32)) { set_err("too many work units in one batch"); return SRD_ERR_ARG; }
+  if (units) TRY(stream_units(c, s, a, units, h.n_multi, (uint8_t*)(uintptr_t)base, nullptr));
+  scatter_finish_kernel<<<grid_for(n), 256, 0, s>>>(a);
+  LAUNCHED(s, "scatter_finish_kernel");
   return 0;
 }
 

@@ -4,11 +4,13 @@
 // unit's descriptor holds (SegUnit), what describes a batch of entries cut into
 // units (UnitArgs, read through a view: a segment table, or ranges, each its
 // own entry of one segment -- the gather's hits, the append's and the live
-// compaction's payloads), and how an entry's CRC-32 is put together from its
-// units' raw CRCs.  Plain integer code shared by the layout kernels
-// (srd_segments.hip), the unit / terms / combine kernels (srd_units.hip), the
-// streaming kernel (srd_stream.hip), the host glue (srd_ops.hip) and a CPU
-// check (tests/sanitize_segments/segments_check.cpp): outside HIP the
+// compaction's payloads -- or, for the scatter read, ranges delivered into a
+// segment table of destinations), and how an entry's CRC-32 is put together
+// from its units' raw CRCs.  Plain integer code shared by the layout kernels
+// (srd_segments.hip, srd_scatter.hip), the unit / terms / combine kernels
+// (srd_units.hip), the streaming kernel (srd_stream.hip), the host glue
+// (srd_ops.hip) and CPU checks (tests/sanitize_segments/segments_check.cpp,
+// tests/sanitize_scatter/scatter_check.cpp): outside HIP the
 // qualifiers are empty.  The entry layout (slots, base, the new tail, the error
 // word) is the append's (srd_append.h) as it is.
 //
@@ -97,7 +99,7 @@ SRD_GA_HD SegEntry seg_entry_layout(SegP segs, uint64_t s0, uint64_t s1, LenP sr
 // A work unit: a piece of one segment.
 struct SegUnit {
   uint64_t src;  // address of its first source byte
-  uint64_t dst;  // file offset of its first byte in the store
+  uint64_t dst;  // offset of its first byte from the streaming kernel's out (the appends: its file offset in the store)
   uint64_t end;  // offset of its end inside its entry (the combine's weight; a single unit: the entry's length)
   uint32_t ent;  // its entry
   uint32_t lf;   // seg_unit_lf
@@ -181,14 +183,14 @@ struct UnitArgs {
   const uint8_t* file;
   const uint64_t *start, *end;
   // a table: entry i is the segments first[i] .. first[i + 1)
-  const uint64_t* srcs;  // [2 n_src] the source table on the device: address, length
+  const uint64_t* srcs;  // [2 n_src] the source table on the device: address, length (the scatter: of destinations)
   const srd_segment* segs;
   const uint64_t* first;  // [n + 1]
   uint64_t* len;          // [n] the entries' lengths
   uint64_t* soff;         // [n_segs] a segment's offset inside its entry
   uint64_t* sun;          // [n_segs] its unit count (upre's addends)
   uint32_t* sent;         // [n_segs] its entry
-  uint64_t dst0;   // a multiple of 64
+  uint64_t dst0;   // a multiple of 64 (the scatter: the address that out stands for, a multiple of 16)
   bool pad;        // an entry's last unit zeroes up to the next 64-byte boundary of the output
   SegUnit* unit;   // [n_units] the unit table
   uint64_t n_units;
@@ -196,7 +198,8 @@ struct UnitArgs {
   uint32_t* crc;   // [n] an entry's CRC32
 };
 // (nothing is materialised for ranges: their unit count is eun[s], their unit
-// prefix upre[s], and the entry's first unit upre[i])
+// prefix upre[s], and the entry's first unit upre[i]); dst is where a
+// segment's first byte goes, as an offset from the streaming kernel's out
 struct RangeView {
   static SRD_GA_HD uint64_t addr(const UnitArgs& a, uint64_t s) { return (uint64_t)(uintptr_t)a.file + a.start[s]; }
   static SRD_GA_HD uint64_t len(const UnitArgs& a, uint64_t s) { return a.end[s] - a.start[s]; }
@@ -204,6 +207,7 @@ struct RangeView {
   static SRD_GA_HD uint64_t ent(const UnitArgs&, uint64_t s) { return s; }
   static SRD_GA_HD uint64_t first(const UnitArgs&, uint64_t i) { return i; }
   static SRD_GA_HD uint64_t ent_len(const UnitArgs& a, uint64_t i) { return a.end[i] - a.start[i]; }
+  static SRD_GA_HD uint64_t dst(const UnitArgs& a, uint64_t s) { return a.dst0 + a.off[s]; }
 };
 struct TableView {
   static SRD_GA_HD uint64_t addr(const UnitArgs& a, uint64_t s) { return a.srcs[2 * a.segs[s].src] + a.segs[s].off; }
@@ -212,6 +216,24 @@ struct TableView {
   static SRD_GA_HD uint64_t ent(const UnitArgs& a, uint64_t s) { return a.sent[s]; }
   static SRD_GA_HD uint64_t first(const UnitArgs& a, uint64_t i) { return a.first[i]; }
   static SRD_GA_HD uint64_t ent_len(const UnitArgs& a, uint64_t i) { return a.len[i]; }
+  static SRD_GA_HD uint64_t dst(const UnitArgs& a, uint64_t s) { return a.dst0 + a.off[a.sent[s]] + a.soff[s]; }
+};
+// The scatter read (srd_scatter.h): entry i is the range [start[i], end[i]) of
+// file, delivered in order into the segments first[i] .. first[i + 1) of a
+// table of DESTINATIONS -- segment s takes the entry's bytes from soff[s] on
+// and puts them at its table address + off, an offset from dst0, the 16-byte
+// boundary at or below the lowest table address.  A unit's below / behind
+// counts are the segment's, so its loads stay inside the payload.
+struct ScatterView {
+  static SRD_GA_HD uint64_t addr(const UnitArgs& a, uint64_t s) {
+    return (uint64_t)(uintptr_t)a.file + a.start[a.sent[s]] + a.soff[s];
+  }
+  static SRD_GA_HD uint64_t len(const UnitArgs& a, uint64_t s) { return a.segs[s].len; }
+  static SRD_GA_HD uint64_t soff(const UnitArgs& a, uint64_t s) { return a.soff[s]; }
+  static SRD_GA_HD uint64_t ent(const UnitArgs& a, uint64_t s) { return a.sent[s]; }
+  static SRD_GA_HD uint64_t first(const UnitArgs& a, uint64_t i) { return a.first[i]; }
+  static SRD_GA_HD uint64_t ent_len(const UnitArgs& a, uint64_t i) { return a.end[i] - a.start[i]; }
+  static SRD_GA_HD uint64_t dst(const UnitArgs& a, uint64_t s) { return a.srcs[2 * a.segs[s].src] + a.segs[s].off - a.dst0; }
 };
 // an entry's first unit (an entry with units has a segment)
 template <class View>
@@ -222,11 +244,12 @@ SRD_GA_HD uint64_t unit_first(const UnitArgs& a, uint64_t i) {
 // upre[s + 1]; of a range, that is chunk u - upre[i] of range i (srd_gather.h:
 // the destination is 64-aligned, so the cut is the chunk cut, the below /
 // behind counts are taken against the range itself, and end is the chunk's end
-// inside it)
+// inside it).  The destination is the view's: the appends' and the gather's at
+// dst0 + off[ent] + soff, the scatter's wherever its segment points.
 template <class View>
 SRD_GA_HD SegUnit unit_of(const UnitArgs& a, uint64_t u) {
   const uint64_t s = gather_unit_hit(a.upre, a.n_segs, u), off = View::soff(a, s), ent = View::ent(a, s), k = a.eun[ent];
-  SegUnit x = seg_unit(View::addr(a, s), a.dst0 + a.off[ent] + off, off, View::len(a, s), u - a.upre[s], (uint32_t)ent, k);
+  SegUnit x = seg_unit(View::addr(a, s), View::dst(a, s), off, View::len(a, s), u - a.upre[s], (uint32_t)ent, k);
   if (a.pad && u + 1 == unit_first<View>(a, ent) + k) x.lf |= SEG_LF_PAD;
   return x;
 }

@@ -72,7 +72,7 @@ EXPORTS = [
     "srd_stream_probe_device", "srd_ctx_multi_shard_ms",
     "srd_index_table_apply_device", "srd_index_table_export_device", "srd_batch_delete_hashed_device",
     "srd_payload_gather_device", "srd_batch_append_device", "srd_compact_live_device",
-    "srd_batch_append_segments_device",
+    "srd_batch_append_segments_device", "srd_payload_scatter_device",
 ]
 
 
@@ -124,7 +124,8 @@ class CompactStats(C.Structure):
 
 
 class Segment(C.Structure):
-    """srd_segment (include/srd_amd.h): the bytes sources[src][off : off + len]"""
+    """srd_segment (include/srd_amd.h): the bytes sources[src][off : off + len]
+    (srd_payload_scatter_device: of its destination table)"""
     _fields_ = [("src", C.c_uint32), ("reserved", C.c_uint32), ("off", C.c_uint64), ("len", C.c_uint64)]
 
 
@@ -219,6 +220,8 @@ def lib():
         L.srd_batch_append_device.argtypes = [vp, vp, u64, vp, vp, vp, u64, u32, u64, vp, u64, C.POINTER(u64), vp, vp]
         L.srd_batch_append_segments_device.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), u64, vp, u64, vp, vp, u64, u32,
                                                        u64, vp, u64, C.POINTER(u64), vp, vp]
+        L.srd_payload_scatter_device.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(vp), C.POINTER(u64), u64, vp, u64,
+                                                 vp, u32, vp, vp, vp]
         L.srd_compact_live_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(CompactStats)]
         L.srd_iter_entries_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
         L.srd_estimate_compaction_savings_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
@@ -1020,6 +1023,117 @@ def batch_append_segments_device(src_ptrs, src_lens, d_segs: int, n_segs: int, d
     return int(nt.value)
 
 
+def _segment_table(entries, dev):
+    """entries[i] as a sequence of contiguous tensors of any dtype on `dev`, taken
+    as their bytes: the table {(data_ptr, nbytes): index} of the distinct tensors,
+    the srd_segment tuples (whole tensors), the entries' first segments (n + 1)
+    and the tensors (to keep them alive).  ValueError for anything else."""
+    import torch
+    table, keep = {}, []
+    segs, first = [], [0]
+    for ent in entries:
+        if isinstance(ent, torch.Tensor) or isinstance(ent, (bytes, bytearray, str)):
+            raise ValueError("an entry must be a sequence of tensors")
+        for t in ent:
+            if not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous():
+                raise ValueError("a segment must be a contiguous tensor on the store's device")
+            nb = t.numel() * t.element_size()
+            k = table.setdefault((t.data_ptr(), nb), len(table))
+            keep.append(t)
+            segs.append((k, 0, 0, nb))
+        first.append(len(segs))
+    return table, segs, first, keep
+
+
+def _segments_to_device(segs, dev):
+    import torch
+    seg_arr = (Segment * max(len(segs), 1))(*segs)
+    return torch.from_numpy(np.frombuffer(seg_arr, np.uint8).copy()).to(dev)
+
+
+# srd_payload_scatter_device (include/srd_amd.h): d_status holds GATHER_* or
+SCATTER_BAD_LENGTH = 4  # SRD_SCATTER_BAD_LENGTH: the segments' lengths do not sum to the payload's
+
+
+class ScatterResult:
+    """What srd_payload_scatter_device reported for n queries: the host arrays
+    `status` (GATHER_NONE / _OK / _BAD_CRC / _BAD_RANGE, SCATTER_BAD_LENGTH) and
+    `crc_computed` (0 where nothing was delivered).  The payloads themselves are
+    in the caller's tensors."""
+
+    def __init__(self, status, crc_computed):
+        self.status, self.crc_computed = status, crc_computed
+
+    def __len__(self):
+        return len(self.status)
+
+    def is_valid_checksum(self):
+        """EntryHandle::is_valid_checksum per query, GatherResult's rule: [bool |
+        None] (None: no hit -- a read's None or a BAD_RANGE).  ValueError if a
+        query's tensors did not hold exactly its payload's bytes (BAD_LENGTH):
+        nothing was delivered there, so there is no handle to judge."""
+        bad = [i for i, s in enumerate(self.status) if s == SCATTER_BAD_LENGTH]
+        if bad:
+            raise ValueError(f"the segments of queries {bad[:8]} do not hold exactly their payloads' bytes")
+        return [True if s == GATHER_OK else False if s == GATHER_BAD_CRC else None for s in self.status]
+
+
+def payload_scatter_device(d_file: int, file_len: int, d_start: int, d_end: int, n: int, dst_ptrs, dst_lens,
+                           d_segs: int, n_segs: int, d_seg_first: int, flags: int = 0, d_status: int | None = None,
+                           d_crc_computed: int | None = None, ctx: "Context | None" = None,
+                           stream: int | None = None) -> None:
+    """srd_payload_scatter_device as it is (the destination table as host
+    sequences of device addresses and lengths, device pointers for the rest):
+    ordered on `stream` (default: the context stream), waits once and returns
+    with the copy enqueued.  SrdError carries the refusal's message and `.rc`."""
+    ctx = ctx or default_ctx()
+    _same_len(dst_ptrs, dst_lens, "destination pointers and destination lengths")
+    k = len(dst_ptrs)
+    ptrs = (C.c_void_p * max(k, 1))(*[int(p) for p in dst_ptrs])
+    lens = (C.c_uint64 * max(k, 1))(*[int(x) for x in dst_lens])
+    rc = lib().srd_payload_scatter_device(ctx.h, C.c_void_p(d_file), file_len, C.c_void_p(d_start), C.c_void_p(d_end), n,
+                                          ptrs, lens, k, C.c_void_p(d_segs), n_segs, C.c_void_p(d_seg_first), flags,
+                                          C.c_void_p(d_status), C.c_void_p(d_crc_computed),
+                                          C.c_void_p(stream if stream is not None else ctx.stream))
+    if rc != 0:
+        e = SrdError(f"srd error {rc}: {lib().srd_last_error().decode()}")
+        e.rc = rc
+        raise e
+
+
+def _scatter_table(d_file: int, file_len: int, st, en, prep, ctx: Context) -> ScatterResult:
+    """scatter_ranges behind _segment_table (prep)."""
+    import torch
+    table, segs, first, _keep = prep  # (the tensors live until the host has waited)
+    dev, n = st.device, st.numel()
+    if len(first) != n + 1:
+        raise ValueError("Mismatched lengths for ranges and entries.")
+    status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    crc = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    if n:
+        d_segs = _segments_to_device(segs, dev)
+        d_first = torch.from_numpy(np.array(first, np.int64)).to(dev)
+        _after_torch(ctx, dev)
+        try:
+            payload_scatter_device(d_file, file_len, st.data_ptr(), en.data_ptr(), n, [p for p, _ in table],
+                                   [nb for _, nb in table], d_segs.data_ptr(), len(segs), d_first.data_ptr(), 0,
+                                   status.data_ptr(), crc.data_ptr(), ctx)
+        finally:
+            _sync_ctx(ctx, dev)  # (after a refusal too: the ranges may be temporaries still being written)
+    return ScatterResult(status[:n].cpu().numpy(), crc[:n].cpu().numpy().view(np.uint32))
+
+
+def scatter_ranges(d_file: int, file_len: int, st, en, entries, ctx: "Context | None" = None) -> ScatterResult:
+    """The payloads of the ranges [st[i], en[i]) (device int64 tensors, as the
+    read and iterator calls write them) delivered into entries[i], a sequence of
+    contiguous tensors of any dtype on the ranges' device, taken as their bytes
+    in order, and checked against their stored checksums
+    (srd_payload_scatter_device; one destination per distinct (data_ptr,
+    nbytes)).  §10's stream rule: the context stream waits for torch's current
+    stream first, the host for the context stream at the end."""
+    return _scatter_table(d_file, file_len, st, en, _segment_table(entries, st.device), ctx or default_ctx())
+
+
 class DeviceIndex:
     """The KeyIndexer adopted on the GPU: an open-addressing table in HBM built
     from n unique (key_hash, packed) device pairs -- e.g. the index arrays of a
@@ -1189,6 +1303,23 @@ class DeviceIndex:
     def _gather(self, d_file: int, file_len: int, hashes, verify, flags: int) -> GatherResult:
         st, en, _keep = self._ranges_device(d_file, file_len, hashes, verify)  # (alive until the gather has waited)
         return gather_ranges(d_file, file_len, st, en, flags, self.ctx)
+
+    def batch_scatter(self, d_file: int, file_len: int, hashes, entries, non_hashed_keys=None) -> ScatterResult:
+        """batch_read_hashed_keys with every payload delivered into the caller's
+        own tensors (entries[i]: scatter_ranges' rule) and checked: the look-up
+        and srd_payload_scatter_device on the device -- an EntryStream read into
+        the caller's buffers (entry_stream.rs:76-91) plus
+        EntryHandle::is_valid_checksum for each query."""
+        if non_hashed_keys is not None:
+            _same_len(non_hashed_keys, hashes, "hashed and non-hashed keys")
+        v = compute_hash_batch(non_hashed_keys, self.ctx) if non_hashed_keys is not None else None
+        return self._scatter(d_file, file_len, hashes, v, entries)
+
+    def _scatter(self, d_file: int, file_len: int, hashes, verify, entries) -> ScatterResult:
+        _same_len(hashes, entries, "key hashes and entries")
+        prep = _segment_table(entries, self.table.device)  # (the ValueErrors: before any call)
+        st, en, _keep = self._ranges_device(d_file, file_len, hashes, verify)  # (alive until the scatter has waited)
+        return _scatter_table(d_file, file_len, st, en, prep, self.ctx)
 
     def batch_read(self, d_file: int, file_len: int, keys):
         """batch_read (data_store.rs:1111-1115): host keys, hashed and verified on the device."""
@@ -1457,21 +1588,8 @@ class DeviceStore:
         if not n:
             return self._tail
         dev = self.buf.device
-        srcs, keep = {}, []
-        segs, first = [], [0]
-        for ent in entries:
-            if isinstance(ent, torch.Tensor) or isinstance(ent, (bytes, bytearray, str)):
-                raise ValueError("an entry must be a sequence of tensors")
-            for t in ent:
-                if not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous():
-                    raise ValueError("a segment must be a contiguous tensor on the store's device")
-                nb = t.numel() * t.element_size()
-                k = srcs.setdefault((t.data_ptr(), nb), len(srcs))
-                keep.append(t)
-                segs.append((k, 0, 0, nb))
-            first.append(len(segs))
-        seg_arr = (Segment * max(len(segs), 1))(*segs)
-        d_segs = torch.from_numpy(np.frombuffer(seg_arr, np.uint8).copy()).to(dev)
+        srcs, segs, first, keep = _segment_table(entries, dev)
+        d_segs = _segments_to_device(segs, dev)
         d_first = self.index._as_dev(np.array(first, np.uint64))
         d_hashes = self.index._as_dev(hashes)
         d_mo = torch.empty(n, dtype=torch.int64, device=dev)
@@ -1647,6 +1765,39 @@ class DeviceStore:
     def batch_gather_hashed_keys(self, hashes, non_hashed_keys=None, flags: int = 0) -> GatherResult:
         """batch_read_hashed_keys (data_store.rs:1111-1158) with the payloads verified."""
         return self.index.batch_gather(self.buf.data_ptr(), self._tail, hashes, non_hashed_keys, flags)
+
+    # -- verified reads into the caller's own tensors -----------------------------------------
+
+    def batch_read_into_hashed_keys(self, hashes, entries, non_hashed_keys=None) -> ScatterResult:
+        """batch_read_hashed_keys (data_store.rs:1111-1158) with every payload read
+        into the caller's buffers piece by piece, as an EntryStream read does
+        (entry_stream.rs:76-91), and checked (EntryHandle::is_valid_checksum):
+        entries[i] is a sequence of contiguous tensors of any dtype on the store's
+        device, taken as their bytes, in order -- batch_write_stream's rule, the
+        tensors being the destinations (one per distinct (data_ptr, nbytes)).
+        The look-up and srd_payload_scatter_device run on the device; no payload
+        length goes through the host.  ScatterResult.status[i]: GATHER_OK /
+        GATHER_BAD_CRC (delivered), GATHER_NONE (no such key: its tensors are left
+        alone), SCATTER_BAD_LENGTH (its tensors do not hold exactly the payload's
+        bytes: left alone).  Anything that is not such a tensor raises ValueError
+        before any call; a tensor inside the store's own buffer raises SrdError."""
+        if not len(entries) and not len(hashes):
+            return ScatterResult(np.zeros(0, np.uint8), np.zeros(0, np.uint32))
+        return self.index.batch_scatter(self.buf.data_ptr(), self._tail, hashes, entries, non_hashed_keys)
+
+    def batch_read_into(self, keys, entries) -> ScatterResult:
+        """batch_read (data_store.rs:1105-1109) into the caller's tensors, each entry
+        an EntryStream read (entry_stream.rs:76-91): compute_hash_batch, then
+        batch_read_into_hashed_keys with every read verified by its key's own tag."""
+        _same_len(keys, entries, "keys and entries")
+        if not len(keys):
+            return ScatterResult(np.zeros(0, np.uint8), np.zeros(0, np.uint32))
+        h = compute_hash_batch(keys, self.ctx)
+        return self.index._scatter(self.buf.data_ptr(), self._tail, h, h, entries)
+
+    def read_into(self, key: bytes, segments) -> int:
+        """One entry read into `segments` (entry_stream.rs:76-91): its status."""
+        return int(self.batch_read_into([key], [segments]).status[0])
 
     def verify(self, keys):
         """The batched is_valid_checksum of `keys` (no payload is copied):
