@@ -902,6 +902,129 @@ int srd_compact_live_device(srd_ctx *ctx, const void *d_table, uint64_t table_by
                             void *d_new_table, uint64_t new_table_bytes,
                             srd_compact_stats *stats);
 
+/* ---- TTL entries: namespaced keys, expiry reads, eviction and the sweep ----
+ *   srd_namespace_hash_batch[_device] <- NamespaceHasher::namespace
+ *                                (src/utils/namespace_hasher.rs:33-65) followed
+ *                                by compute_hash of the namespaced key
+ *   srd_ttl_resolve[_keys]_device <- the decision of StorageCacheExt::
+ *                                read_with_ttl (extensions/src/storage_cache_ext.rs:72-107)
+ *                                for a batch, nothing written
+ *   srd_ttl_evict_device      <- that read's delete(namespaced key) of an
+ *                                expired entry (storage_cache_ext.rs:91-96),
+ *                                for the batch's expired keys
+ *   srd_ttl_sweep_device      <- no counterpart: the reference evicts an
+ *                                expired entry only when somebody reads it
+ * The contract (write_with_ttl, storage_cache_ext.rs:23-58; TTL_PREFIX = the 5
+ * bytes F7 74 74 6C FD, extensions/src/constants.rs:20-42): the namespaced key
+ * of `key` under `prefix` is the 16 bytes le64(xxh3_64(prefix)) ||
+ * le64(xxh3_64(key)); the entry is stored under key_hash = xxh3_64(namespaced
+ * key); its payload is le64(expiry) || value with expiry =
+ * now_secs.saturating_add(ttl_secs).  Writing needs no call of its own: the
+ * payload goes through any write or append call above under that key_hash.
+ * A read at `now`: absent -> NotFound; payload below 8 bytes -> InvalidData
+ * ("Data too short to contain TTL"); now >= expiry -> the entry is deleted,
+ * None; otherwise the value.  The read's tag check compares the stored tag
+ * with the tag of the hash the entry was found by, so it cannot fire. */
+#define SRD_TTL_NOT_FOUND 0u  /* absent, removed, or the indexed entry is a tombstone / out of range */
+#define SRD_TTL_LIVE      1u
+#define SRD_TTL_EXPIRED   2u  /* now >= expiry */
+#define SRD_TTL_TOO_SHORT 3u  /* payload < 8 bytes: the reference's InvalidData */
+
+/* Key i = d_keys[d_offs[i] .. d_offs[i] + d_lens[i]) (device).  d_hash_out[i] =
+ * xxh3_64 of key i's namespaced key under prefix_hash = xxh3_64(prefix);
+ * d_ns_out (nullable; 16 n bytes, 8-byte aligned) receives the namespaced keys
+ * themselves.  Reads the keys, writes the two outputs, nothing else.
+ * Asynchronous on `stream` (NULL: the context's): returns with the kernel
+ * enqueued.  SRD_ERR_ARG: a NULL context, a missing array with n > 0, d_ns_out
+ * not 8-byte aligned. */
+int srd_namespace_hash_batch_device(srd_ctx *ctx, uint64_t prefix_hash, const uint8_t *d_keys,
+                                    const uint64_t *d_offs, const uint64_t *d_lens, uint64_t n,
+                                    uint8_t *d_ns_out /* 16 n, nullable */, uint64_t *d_hash_out /* n */,
+                                    void *stream);
+/* The same for host arrays (keys[0 .. klen), every key inside it: SRD_ERR_ARG
+ * otherwise), as srd_xxh3_64_batch: staged, hashed and copied back on the
+ * context stream; synchronises.  ns_out is nullable. */
+int srd_namespace_hash_batch(srd_ctx *ctx, uint64_t prefix_hash, const uint8_t *keys, uint64_t klen,
+                             const uint64_t *offs, const uint64_t *lens, uint64_t n,
+                             uint8_t *ns_out /* 16 n, nullable */, uint64_t *hash_out /* n */);
+
+/* read_with_ttl's decision for n key hashes (of namespaced keys) against the
+ * live table d_table of the store d_file[0 .. file_len), judged at `now`: per
+ * query the probe (KeyIndexer::get_packed), the indexed entry's metadata with
+ * srd_batch_read_hashed_device's bounds, prepad and tombstone rules, and -- only
+ * when the payload holds them -- the 8 expiry bytes at its start.  No byte
+ * outside [0, file_len) is read, and the call reads only: table and store are
+ * left as they are.
+ *   d_status[i]        SRD_TTL_*
+ *   d_start / d_end    LIVE: the whole payload, its 8 expiry bytes included --
+ *                      srd_payload_gather_device and srd_payload_scatter_device
+ *                      take these ranges as they are, and the stored CRC covers
+ *                      what they stream; every other status: (0, 0), the
+ *                      gather's NONE
+ *   d_expiry[i]        (nullable) the stored expiry for LIVE and EXPIRED, else 0
+ *   d_counts           (nullable, 4 x u64) set to the number of queries per status
+ * A batch is judged against the store as it is when the call runs: a key that
+ * is expired and appears twice is EXPIRED twice (n sequential reference reads
+ * would delete it at the first and say NotFound at the second).
+ * Asynchronous on `stream` (NULL: the context's): returns with the work
+ * enqueued, later work on `stream` sees the outputs.  SRD_ERR_ARG, nothing
+ * written: a NULL context, a table_bytes below the smallest table, a missing
+ * array with n > 0. */
+int srd_ttl_resolve_device(srd_ctx *ctx, const void *d_table, uint64_t table_bytes,
+                           const uint8_t *d_file, uint64_t file_len,
+                           const uint64_t *d_hashes, uint64_t n, uint64_t now,
+                           uint64_t *d_start, uint64_t *d_end, uint64_t *d_expiry /* nullable */,
+                           uint8_t *d_status, uint64_t *d_counts /* 4, nullable */, void *stream);
+/* The same from the raw keys (key i = d_keys[d_offs[i] .. + d_lens[i]), as
+ * srd_namespace_hash_batch_device), hashed inside the same launch: a keyed
+ * read's decision in one kernel, no intermediate arrays.  d_hashes_out[i] = the
+ * key hash query i was looked up by (what srd_ttl_evict_device takes). */
+int srd_ttl_resolve_keys_device(srd_ctx *ctx, const void *d_table, uint64_t table_bytes,
+                                const uint8_t *d_file, uint64_t file_len, uint64_t prefix_hash,
+                                const uint8_t *d_keys, const uint64_t *d_offs, const uint64_t *d_lens,
+                                uint64_t n, uint64_t now, uint64_t *d_hashes_out,
+                                uint64_t *d_start, uint64_t *d_end, uint64_t *d_expiry /* nullable */,
+                                uint8_t *d_status, uint64_t *d_counts /* 4, nullable */, void *stream);
+
+/* srd_batch_delete_hashed_device restricted to the queries with d_status[i] ==
+ * SRD_TTL_EXPIRED (as a resolve call wrote them) and deduplicated: one
+ * tombstone per distinct key among them, in batch order of each key's last
+ * such query, appended at `tail` of the store at d_file (d_file[j] = file byte
+ * j, writable to file_cap bytes; 21 bytes each: a NULL byte, no prepad,
+ * prev_offset = the previous tail, CRC 0xD202EF8D), and the keys removed from
+ * the table.  *n_evicted (nullable) = tombstones written.  Nothing expired:
+ * nothing written, *new_tail = tail.  SRD_ERR_ARG when srd_padded_size(new
+ * tail) > file_cap (nothing written, *new_tail = tail), for n >= 2^31 and for
+ * missing arguments.  On the context stream; synchronises. */
+int srd_ttl_evict_device(srd_ctx *ctx, void *d_table, uint64_t table_bytes, uint64_t *used,
+                         const uint64_t *d_hashes, const uint8_t *d_status, uint64_t n,
+                         uint64_t tail, uint8_t *d_file, uint64_t file_cap,
+                         uint64_t *new_tail, uint64_t *n_evicted);
+
+/* The sweep: every live pair of the table (what srd_index_table_export_device
+ * gives, ascending metadata offset) judged at `now` by the resolve's rule, and
+ * the expired ones evicted -- one tombstone each, in ascending metadata offset
+ * of the entries they remove, written and applied as srd_ttl_evict_device
+ * does.  KEYS ARE NOT STORED, so nothing tells a TTL entry from any other:
+ * EVERY live entry is judged as a TTL entry, its first 8 payload bytes taken
+ * as an expiry.  The call is for stores written only through the TTL writes.
+ * Entries whose payload is below 8 bytes are left alone and counted (n_short).
+ * SRD_TTL_SWEEP_PLAN computes the stats and writes nothing.  *new_tail = tail
+ * when nothing is written.  SRD_ERR_ARG: srd_padded_size(new tail) > file_cap
+ * (nothing written, the stats are reported), unknown flags, missing arguments,
+ * 2^31 or more live pairs.  On the context stream; synchronises; the
+ * workspace comes from the context (srd_ctx_device_bytes counts it). */
+#define SRD_TTL_SWEEP_PLAN 1u
+typedef struct {
+  uint64_t n_judged;     /* live pairs of the table */
+  uint64_t n_expired;    /* of them now >= expiry: the tombstones (to be) written */
+  uint64_t n_short;      /* of them with a payload below 8 bytes: left alone */
+  uint64_t next_expiry;  /* the smallest expiry among the survivors (LIVE); ~0 when there is none */
+} srd_ttl_sweep_stats;
+int srd_ttl_sweep_device(srd_ctx *ctx, void *d_table, uint64_t table_bytes, uint64_t *used,
+                         uint8_t *d_file, uint64_t tail, uint64_t file_cap, uint64_t now,
+                         uint32_t flags, uint64_t *new_tail, srd_ttl_sweep_stats *stats);
+
 /* Synthetic store of the BASELINE configs written on the device (the
  * checksum-on-append writer of data_store.rs:847-939 for keys
  * "bench-key-{i}" and counter-mode splitmix64 payloads).  lens==NULL ->

@@ -32,8 +32,11 @@
 //     srd_scatter.hip         verified payloads read into device segments: layout and finish around the unit kernels
 //     srd_table.h             the lookup table's rule: slot states, probe, claim, size arithmetic (the host entries
 //                             and a CPU check use it too)
+//     srd_ttl.h               the TTL cache's rule: the read's range rule (entry_range), the verdict on an indexed
+//                             entry (ttl_judge), the expiry, eviction's choice among a batch (a CPU check uses it too)
 //     srd_index.hip           lookup table build and reads, iterator, compaction
 //     srd_index_live.hip      the table kept live: apply, export, batched delete; the live compaction's two steps
+//     srd_ttl.hip             the TTL cache: namespaced key hash, the batched read's decision, the sweep
 //     srd_probe.hip           stream probe
 //   host code (in include order: each file uses only the ones above it)
 //     srd_host.cpp / .h       no-HIP parsers (shard cuts, batch layout)
@@ -47,7 +50,7 @@
 //     srd_multi.hip           multi-GPU open
 //     srd_ops.hip             probe, batch digests, synth, writer, table / reads / maintenance, iterator,
 //                             compaction, payload gather and scatter, device append, segment append, live
-//                             compaction
+//                             compaction, TTL cache
 //   this file               error / build-info entries, stamps read-outs, host self-test
 //
 // Glue scans/compactions use hipCUB (library primitives, like calling
@@ -86,8 +89,10 @@
 #include "srd_segments.hip"
 #include "srd_scatter.hip"
 #include "srd_table.h"
+#include "srd_ttl.h"
 #include "srd_index.hip"
 #include "srd_index_live.hip"
+#include "srd_ttl.hip"
 #include "srd_probe.hip"
 
 using namespace srd;

@@ -241,6 +241,7 @@ enum BufId {
   B_AP_END, B_AP_NZ,  // device append (on top of the gather's)
   B_CL_XK, B_CL_XP, B_CL_LEN, B_CL_MO, B_CL_PACKED, B_CL_CNT,  // live compaction (on top of the export's, the iterator's and the append's)
   B_SG_SRC, B_SG_LEN, B_SG_OFF, B_SG_UN, B_SG_UPRE, B_SG_ENT,  // segment append (on top of the append's)
+  B_TT_CNT, B_TT_XQ, B_TT_FLAG, B_TT_POS,  // TTL eviction and sweep (on top of the delete's, the apply's and the export's)
   B_COUNT_
 };
 

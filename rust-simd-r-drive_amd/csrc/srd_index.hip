@@ -23,22 +23,8 @@ __global__ void idx_get_packed_kernel(Table t, const uint64_t* q, uint64_t n, ui
     out[i] = table_get(t, q[i]);
 }
 
-// The payload range of the entry whose metadata is at `off`, with the
-// reference's bounds, prepad and tombstone rules (read_entry_with_context
-// :524-553, par_iter_entries :322-353, EntryIterator::next
-// entry_iterator.rs:85-118); false for None (out of range / tombstone).
-__device__ __forceinline__ bool entry_range(const uint8_t* file, uint64_t flen, uint64_t off, uint64_t* start,
-                                            uint64_t* end) {
-  if (off + 20 > flen) return false;
-  const uint64_t prev = ld_u64_unaligned(file, off + 8);  // EntryMetadata.prev_offset
-  uint64_t s = prev + prepad64(prev);
-  if (off > prev && off - prev == 1 && file[prev] == 0) s = prev;  // tombstone: no prepad
-  if (s >= off) return false;
-  if (off - s == 1 && file[s] == 0) return false;  // tombstone -> None
-  *start = s;
-  *end = off;
-  return true;
-}
+// (entry_range, the payload range of the entry whose metadata is at `off`, is
+// srd_ttl.h's: the TTL verdict and a CPU check compile the same text)
 
 // par_iter_entries over the index: flags, ranges and the kept bytes
 // (range + metadata, EntryHandle::file_size) for estimate_compaction_savings

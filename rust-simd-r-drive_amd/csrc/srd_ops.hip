@@ -500,6 +500,35 @@ extern "C" int srd_index_table_export_device(srd_ctx* c, const void* d_table, ui
   return 0;
 }
 
+// nk tombstones at `tail` on the context stream, one per flagged hash of q[n]
+// in the order pos gives (the exclusive sum of flag; nk >= 1 its total), and
+// the keys removed from the table: the delete's second half, and what a TTL
+// eviction ends in.  Refused with nothing written when the tombstones do not
+// fit file_cap; waits for the stream at the end.
+static int tombs_commit(Ctx* c, void* d_table, uint64_t table_bytes, uint64_t* used, const uint64_t* q,
+                        const uint32_t* flag, const uint32_t* pos, uint64_t n, uint64_t nk, uint64_t tail,
+                        uint8_t* d_file, uint64_t file_cap, uint64_t* new_tail) {
+  const uint64_t nt = tail + 21 * nk;
+  if (srd_padded_size(nt) > file_cap) { set_err("file_cap too small for the tombstones"); return SRD_ERR_ARG; }
+  TRY(ensure(c, B_LV_ENT, nk * sizeof(srd_write_entry)));
+  TRY(ensure(c, B_LV_TOMB, nk));
+  TRY(ensure(c, B_WKH, nk * 8));
+  TRY(ensure(c, B_WMO, nk * 8));
+  live_tomb_entries_kernel<<<grid_for(n), 256, 0, c->stream>>>(q, flag, pos, n, tail, P<srd_write_entry>(c, B_LV_ENT));
+  LAUNCHED(c->stream, "live_tomb_entries_kernel");
+  HIPCHK(hipMemsetAsync(P<void>(c, B_LV_TOMB), 1, nk, c->stream));
+  // (a tombstone reads no payload or key bytes: d_file only stands for the payload base)
+  TRY(launch_write(c, c->stream, d_file, nullptr, P<srd_write_entry>(c, B_LV_ENT), nk, d_file, 0,
+                   P<uint64_t>(c, B_WKH), P<uint64_t>(c, B_WMO)));
+  // every kept key was present and every pair is a tombstone: the apply
+  // removes them all and needs no new slot, so it cannot be refused
+  TRY(apply_impl(c, d_table, table_bytes, used, P<uint64_t>(c, B_WKH), P<uint64_t>(c, B_WMO), P<uint8_t>(c, B_LV_TOMB),
+                 nk, nullptr, c->stream));
+  HIPCHK(spin_sync(c->stream));
+  *new_tail = nt;
+  return 0;
+}
+
 extern "C" int srd_batch_delete_hashed_device(srd_ctx* c, void* d_table, uint64_t table_bytes, uint64_t* used,
                                               const uint64_t* d_hashes, uint64_t n, uint64_t tail, uint8_t* d_file,
                                               uint64_t file_cap, uint64_t* new_tail, uint64_t* n_deleted) {
@@ -522,25 +551,7 @@ extern "C" int srd_batch_delete_hashed_device(srd_ctx* c, void* d_table, uint64_
   uint64_t nk = 0;
   TRY(scan_sum_total(c, flag, pos, n, c->stream, &nk));
   if (!nk) return 0;  // (the reference returns the unchanged tail: data_store.rs:1011-1014)
-  const uint64_t nt = tail + 21 * nk;
-  if (srd_padded_size(nt) > file_cap) { set_err("file_cap too small for the tombstones"); return SRD_ERR_ARG; }
-  TRY(ensure(c, B_LV_ENT, nk * sizeof(srd_write_entry)));
-  TRY(ensure(c, B_LV_TOMB, nk));
-  TRY(ensure(c, B_WKH, nk * 8));
-  TRY(ensure(c, B_WMO, nk * 8));
-  live_tomb_entries_kernel<<<grid_for(n), 256, 0, c->stream>>>(d_hashes, flag, pos, n, tail,
-                                                              P<srd_write_entry>(c, B_LV_ENT));
-  LAUNCHED(c->stream, "live_tomb_entries_kernel");
-  HIPCHK(hipMemsetAsync(P<void>(c, B_LV_TOMB), 1, nk, c->stream));
-  // (a tombstone reads no payload or key bytes: d_file only stands for the payload base)
-  TRY(launch_write(c, c->stream, d_file, nullptr, P<srd_write_entry>(c, B_LV_ENT), nk, d_file, 0,
-                   P<uint64_t>(c, B_WKH), P<uint64_t>(c, B_WMO)));
-  // every kept key was present and every pair is a tombstone: the apply
-  // removes them all and needs no new slot, so it cannot be refused
-  TRY(apply_impl(c, d_table, table_bytes, used, P<uint64_t>(c, B_WKH), P<uint64_t>(c, B_WMO), P<uint8_t>(c, B_LV_TOMB),
-                 nk, nullptr, c->stream));
-  HIPCHK(spin_sync(c->stream));
-  *new_tail = nt;
+  TRY(tombs_commit(c, d_table, table_bytes, used, d_hashes, flag, pos, n, nk, tail, d_file, file_cap, new_tail));
   if (n_deleted) *n_deleted = nk;
   return 0;
 }
@@ -1216,4 +1227,201 @@ extern "C" int srd_compact_live_device(srd_ctx* c, const void* d_table, uint64_t
   stats->n_crc_bad = h.n_bad;
   if (h.n_bad) TRY(read_small(c, s, {rd(en + h.first, &stats->first_bad)}));  // (a corrupt store only) its source metadata offset
   return 0;
+}
+
+// ---------------------------------------------------------------------------
+// The TTL cache (srd_ttl.h, srd_ttl.hip): namespaced key
+// hashes, the batched read's decision, eviction and the sweep
+extern "C" int srd_namespace_hash_batch_device(srd_ctx* c, uint64_t prefix_hash, const uint8_t* d_keys,
+                                               const uint64_t* d_offs, const uint64_t* d_lens, uint64_t n,
+                                               uint8_t* d_ns_out, uint64_t* d_hash_out, void* stream) {
+  if (!c || ((uintptr_t)d_ns_out & 7) || (n && (!d_keys || !d_offs || !d_lens || !d_hash_out))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  if (!n) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream_of(c, stream);
+  ns_hash_kernel<<<blocks(n, 256), 256, 0, s>>>(NsKeys{d_keys, d_offs, d_lens, prefix_hash}, n, (uint64_t*)d_ns_out,
+                                                d_hash_out);
+  LAUNCHED(s, "ns_hash_kernel");
+  return 0;
+}
+
+extern "C" int srd_namespace_hash_batch(srd_ctx* c, uint64_t prefix_hash, const uint8_t* keys, uint64_t klen,
+                                        const uint64_t* offs, const uint64_t* lens, uint64_t n, uint8_t* ns_out,
+                                        uint64_t* hash_out) {
+  if (!c || (n && (!offs || !lens || !hash_out))) { set_err("bad argument"); return SRD_ERR_ARG; }
+  DevTmp dns;  // (released behind batch_host's wait)
+  if (ns_out && n && dns.alloc(16 * n) != hipSuccess) { set_err("hipMalloc failed"); return SRD_ERR_ALLOC; }
+  return batch_host<uint64_t>(c, keys, klen, offs, lens, n, hash_out, [&](auto db, auto dof, auto dl, auto dout) {
+    TRY(srd_namespace_hash_batch_device(c, prefix_hash, db, dof, dl, n, (uint8_t*)dns.p, dout, nullptr));
+    if (dns.p) HIPCHK(hipMemcpyAsync(ns_out, dns.p, 16 * n, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+  });
+}
+
+// One lane per query or pair, in strides over a grid that fills the machine
+// exactly once -- the blocks of 256 the kernel's registers let a CU hold, asked
+// of the runtime once per kernel -- so that no second, partial round of blocks
+// trails the first and the counts cost one set of atomics per resident block
+template <auto Kernel>
+static unsigned ttl_grid(Ctx* c, uint64_t n) {
+  static const int per_cu = [] {
+    int b = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, Kernel, 256, 0) == hipSuccess && b > 0 ? b : 8;
+  }();
+  return std::min(grid_for(n), c->scan_cus * (unsigned)per_cu);
+}
+
+static int ttl_resolve_run(srd_ctx* c, const void* d_table, uint64_t table_bytes, const uint8_t* d_file, uint64_t flen,
+                           const uint64_t* d_hashes, const NsKeys* keys, uint64_t* d_hashes_out, uint64_t n,
+                           uint64_t now, uint64_t* d_start, uint64_t* d_end, uint64_t* d_expiry, uint8_t* d_status,
+                           uint64_t* d_counts, void* stream) {
+  const bool ins = keys ? keys->keys && keys->offs && keys->lens && d_hashes_out : d_hashes != nullptr;
+  if (!c || !table_ok(d_table, table_bytes) || (n && (!ins || !d_start || !d_end || !d_status || (flen && !d_file)))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream_of(c, stream);
+  if (d_counts) HIPCHK(hipMemsetAsync(d_counts, 0, 32, s));
+  if (!n) return 0;
+  TtlResolveArgs a{};
+  a.t = table_view(d_table, table_bytes);
+  a.file = d_file;
+  a.flen = flen;
+  a.q = d_hashes;
+  if (keys) a.k = *keys;
+  a.q_out = d_hashes_out;
+  a.n = n;
+  a.now = now;
+  a.start = d_start;
+  a.end = d_end;
+  a.expiry = d_expiry;
+  a.status = d_status;
+  a.cnt = (unsigned long long*)d_counts;
+  if (keys)
+    ttl_resolve_kernel<true><<<ttl_grid<ttl_resolve_kernel<true>>(c, n), 256, 0, s>>>(a);
+  else
+    ttl_resolve_kernel<false><<<ttl_grid<ttl_resolve_kernel<false>>(c, n), 256, 0, s>>>(a);
+  LAUNCHED(s, "ttl_resolve_kernel");
+  return 0;
+}
+
+extern "C" int srd_ttl_resolve_device(srd_ctx* c, const void* d_table, uint64_t table_bytes, const uint8_t* d_file,
+                                      uint64_t file_len, const uint64_t* d_hashes, uint64_t n, uint64_t now,
+                                      uint64_t* d_start, uint64_t* d_end, uint64_t* d_expiry, uint8_t* d_status,
+                                      uint64_t* d_counts, void* stream) {
+  return ttl_resolve_run(c, d_table, table_bytes, d_file, file_len, d_hashes, nullptr, nullptr, n, now, d_start, d_end,
+                         d_expiry, d_status, d_counts, stream);
+}
+
+extern "C" int srd_ttl_resolve_keys_device(srd_ctx* c, const void* d_table, uint64_t table_bytes, const uint8_t* d_file,
+                                           uint64_t file_len, uint64_t prefix_hash, const uint8_t* d_keys,
+                                           const uint64_t* d_offs, const uint64_t* d_lens, uint64_t n, uint64_t now,
+                                           uint64_t* d_hashes_out, uint64_t* d_start, uint64_t* d_end,
+                                           uint64_t* d_expiry, uint8_t* d_status, uint64_t* d_counts, void* stream) {
+  const NsKeys k{d_keys, d_offs, d_lens, prefix_hash};
+  return ttl_resolve_run(c, d_table, table_bytes, d_file, file_len, nullptr, &k, d_hashes_out, n, now, d_start, d_end,
+                         d_expiry, d_status, d_counts, stream);
+}
+
+extern "C" int srd_ttl_evict_device(srd_ctx* c, void* d_table, uint64_t table_bytes, uint64_t* used,
+                                    const uint64_t* d_hashes, const uint8_t* d_status, uint64_t n, uint64_t tail,
+                                    uint8_t* d_file, uint64_t file_cap, uint64_t* new_tail, uint64_t* n_evicted) {
+  if (!c || !table_ok(d_table, table_bytes) || !used || !new_tail || n >= (1ull << 31) ||
+      (n && (!d_hashes || !d_status || !d_file))) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  *new_tail = tail;
+  if (n_evicted) *n_evicted = 0;
+  if (!n) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  // the expired queries' hashes, packed in batch order
+  TRY(ensure(c, B_LV_FLAG, n * 4));
+  TRY(ensure(c, B_LV_POS, n * 4));
+  uint32_t* flag = P<uint32_t>(c, B_LV_FLAG);
+  uint32_t* pos = P<uint32_t>(c, B_LV_POS);
+  TRY(ensure_scan(c, flag, pos, n));
+  ttl_candidates_kernel<<<grid_for(n), 256, 0, s>>>(d_status, n, flag);
+  LAUNCHED(s, "ttl_candidates_kernel");
+  uint64_t m = 0;
+  TRY(scan_sum_total(c, flag, pos, n, s, &m));
+  if (!m) return 0;
+  TRY(ensure(c, B_TT_XQ, m * 8));
+  uint64_t* xq = P<uint64_t>(c, B_TT_XQ);
+  ttl_pack_kernel<<<grid_for(n), 256, 0, s>>>(d_hashes, flag, pos, n, xq);
+  LAUNCHED(s, "ttl_pack_kernel");
+  // one tombstone per distinct key among them, at the key's last occurrence:
+  // the apply's dedupe over the packed hashes (the table is not touched)
+  uint32_t log2dc = 6;
+  while ((1ull << log2dc) < 2 * m) log2dc++;
+  const uint64_t dc = 1ull << log2dc;
+  TRY(ensure(c, B_LV_DSLOT, dc * 4));
+  TRY(ensure(c, B_LV_LSLOT, m * 4));
+  TRY(ensure(c, B_TT_FLAG, m * 4));
+  TRY(ensure(c, B_TT_POS, m * 4));
+  LiveArgs a{};
+  a.kh = xq;
+  a.n = m;
+  a.dslot = P<uint32_t>(c, B_LV_DSLOT);
+  a.log2dc = log2dc;
+  a.lslot = P<uint32_t>(c, B_LV_LSLOT);
+  uint32_t* keep = P<uint32_t>(c, B_TT_FLAG);
+  uint32_t* kpos = P<uint32_t>(c, B_TT_POS);
+  TRY(ensure_scan(c, keep, kpos, m));
+  HIPCHK(hipMemsetAsync(a.dslot, 0, dc * 4, s));
+  live_dedupe_kernel<<<grid_for(m), 256, 0, s>>>(a);
+  LAUNCHED(s, "live_dedupe_kernel");
+  ttl_keep_kernel<<<grid_for(m), 256, 0, s>>>(a.dslot, a.lslot, m, keep);
+  LAUNCHED(s, "ttl_keep_kernel");
+  uint64_t nk = 0;
+  TRY(scan_sum_total(c, keep, kpos, m, s, &nk));
+  TRY(tombs_commit(c, d_table, table_bytes, used, xq, keep, kpos, m, nk, tail, d_file, file_cap, new_tail));
+  if (n_evicted) *n_evicted = nk;
+  return 0;
+}
+
+extern "C" int srd_ttl_sweep_device(srd_ctx* c, void* d_table, uint64_t table_bytes, uint64_t* used, uint8_t* d_file,
+                                    uint64_t tail, uint64_t file_cap, uint64_t now, uint32_t flags, uint64_t* new_tail,
+                                    srd_ttl_sweep_stats* stats) {
+  if (stats) *stats = srd_ttl_sweep_stats{0, 0, 0, ~0ull};
+  if (!c || !table_ok(d_table, table_bytes) || !used || !new_tail || !stats || (flags & ~SRD_TTL_SWEEP_PLAN) ||
+      (tail && !d_file)) {
+    set_err("bad argument");
+    return SRD_ERR_ARG;
+  }
+  *new_tail = tail;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  // the live pairs in ascending metadata offset (workspace)
+  uint64_t nl = 0;
+  uint64_t *xk = nullptr, *xp = nullptr;
+  TRY(export_run(c, d_table, table_bytes, &xk, &xp, 0, true, &nl));
+  stats->n_judged = nl;
+  if (!nl) return 0;
+  TRY(ensure(c, B_LV_FLAG, nl * 4));
+  TRY(ensure(c, B_LV_POS, nl * 4));
+  TRY(ensure(c, B_TT_CNT, 64));
+  uint32_t* flag = P<uint32_t>(c, B_LV_FLAG);
+  uint32_t* pos = P<uint32_t>(c, B_LV_POS);
+  unsigned long long* cnt = P<unsigned long long>(c, B_TT_CNT);
+  TRY(ensure_scan(c, flag, pos, nl));
+  HIPCHK(hipMemsetAsync(cnt, 0, 16, s));
+  HIPCHK(hipMemsetAsync(cnt + 2, 0xFF, 8, s));  // the smallest surviving expiry: none
+  ttl_sweep_kernel<<<ttl_grid<ttl_sweep_kernel>(c, nl), 256, 0, s>>>(d_file, tail, xp, nl, now, flag, cnt);
+  LAUNCHED(s, "ttl_sweep_kernel");
+  struct { unsigned long long expired, too_short, next; } h{};
+  uint64_t nk = 0;
+  TRY(scan_sum_total(c, flag, pos, nl, s, &nk, SmallRead{cnt, &h, sizeof h}));
+  if (nk != h.expired) { set_err("internal: the sweep's flags and its count differ"); return SRD_ERR_INTERNAL; }
+  stats->n_expired = h.expired;
+  stats->n_short = h.too_short;
+  stats->next_expiry = h.next;
+  if ((flags & SRD_TTL_SWEEP_PLAN) || !nk) return 0;
+  // the flagged keys are distinct (a table's) and in ascending metadata offset already
+  return tombs_commit(c, d_table, table_bytes, used, xk, flag, pos, nl, nk, tail, d_file, file_cap, new_tail);
 }

@@ -22,6 +22,7 @@ import ctypes as C
 import mmap as _mmap
 import os
 import subprocess
+import time
 
 import numpy as np
 
@@ -73,6 +74,8 @@ EXPORTS = [
     "srd_index_table_apply_device", "srd_index_table_export_device", "srd_batch_delete_hashed_device",
     "srd_payload_gather_device", "srd_batch_append_device", "srd_compact_live_device",
     "srd_batch_append_segments_device", "srd_payload_scatter_device",
+    "srd_namespace_hash_batch_device", "srd_namespace_hash_batch", "srd_ttl_resolve_device",
+    "srd_ttl_resolve_keys_device", "srd_ttl_evict_device", "srd_ttl_sweep_device",
 ]
 
 
@@ -121,6 +124,15 @@ class CompactStats(C.Structure):
 
     def __repr__(self):
         return "CompactStats(" + ", ".join(f"{n}={int(getattr(self, n))}" for n, _ in self._fields_) + ")"
+
+
+class TtlSweepStats(C.Structure):
+    """srd_ttl_sweep_stats (include/srd_amd.h)"""
+    _fields_ = [("n_judged", C.c_uint64), ("n_expired", C.c_uint64), ("n_short", C.c_uint64),
+                ("next_expiry", C.c_uint64)]
+
+    def __repr__(self):
+        return "TtlSweepStats(" + ", ".join(f"{n}={int(getattr(self, n))}" for n, _ in self._fields_) + ")"
 
 
 class Segment(C.Structure):
@@ -223,6 +235,15 @@ def lib():
         L.srd_payload_scatter_device.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(vp), C.POINTER(u64), u64, vp, u64,
                                                  vp, u32, vp, vp, vp]
         L.srd_compact_live_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(CompactStats)]
+        L.srd_namespace_hash_batch_device.argtypes = [vp, u64, vp, vp, vp, u64, vp, vp, vp]
+        L.srd_namespace_hash_batch.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp, vp]
+        L.srd_ttl_resolve_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, vp, vp, vp, vp, vp, vp]
+        L.srd_ttl_resolve_keys_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, vp, vp, u64, u64, vp, vp, vp, vp, vp,
+                                                  vp, vp]
+        L.srd_ttl_evict_device.argtypes = [vp, vp, u64, C.POINTER(u64), vp, vp, u64, u64, vp, u64, C.POINTER(u64),
+                                           C.POINTER(u64)]
+        L.srd_ttl_sweep_device.argtypes = [vp, vp, u64, C.POINTER(u64), vp, u64, u64, u64, u32, C.POINTER(u64),
+                                           C.POINTER(TtlSweepStats)]
         L.srd_iter_entries_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
         L.srd_estimate_compaction_savings_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.srd_compact_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, vp]
@@ -600,6 +621,44 @@ def compute_checksum(data: bytes) -> bytes:
     d = bytes(data)
     v = int(crc32_batch(np.frombuffer(d or b"\x00", np.uint8), [0], [len(d)])[0])
     return v.to_bytes(4, "little")
+
+
+# ---------------------------------------------------------------------------
+# The TTL cache's keys (extensions/src/storage_cache_ext.rs:23-107 over
+# src/utils/namespace_hasher.rs:33-65)
+
+TTL_PREFIX = bytes([0xF7, 0x74, 0x74, 0x6C, 0xFD])  # extensions/src/constants.rs:20-42
+TTL_NOT_FOUND, TTL_LIVE, TTL_EXPIRED, TTL_TOO_SHORT = 0, 1, 2, 3  # SRD_TTL_*
+TTL_SWEEP_PLAN = 1  # SRD_TTL_SWEEP_PLAN
+U64_MAX = (1 << 64) - 1
+
+
+class NamespaceHasher:
+    """NamespaceHasher (namespace_hasher.rs:33-65): `prefix` is hashed once; the
+    namespaced key of `key` is the 16 bytes le64(xxh3_64(prefix)) ||
+    le64(xxh3_64(key)).  Both hashes run on the device."""
+
+    def __init__(self, prefix: bytes, ctx: Context | None = None):
+        self.ctx = ctx or default_ctx()
+        self.prefix = bytes(prefix)
+        self.prefix_hash = compute_hash_batch([self.prefix], self.ctx)[0]
+
+    def _batch(self, keys, want_ns: bool):
+        buf, offs, lens = _blob(keys)
+        n = len(lens)
+        out = np.zeros(max(n, 1), np.uint64)
+        ns = np.zeros(16 * max(n, 1), np.uint8) if want_ns else None
+        _check(lib().srd_namespace_hash_batch(self.ctx.h, self.prefix_hash, _ptr(buf), buf.size if n else 0, _ptr(offs),
+                                              _ptr(lens), n, _ptr(ns) if want_ns else None, _ptr(out)))
+        return ns, out[:n]
+
+    def namespace(self, key: bytes) -> bytes:
+        """namespace_hasher.rs:52-64: the 16-byte namespaced key."""
+        return self._batch([key], True)[0].tobytes()
+
+    def hash_batch(self, keys) -> list[int]:
+        """compute_hash_batch of the keys' namespaced keys: the hashes their entries are stored under."""
+        return [int(x) for x in self._batch(keys, False)[1]]
 
 
 class KeyIndexer:
@@ -1045,6 +1104,19 @@ def _segment_table(entries, dev):
     return table, segs, first, keep
 
 
+def _header_segments(table, segs, first, hdr):
+    """_segment_table's segments with 8 bytes of `hdr` (a device int64[n], added
+    to the table) in front of each entry's: entry i starts with hdr[i]'s bytes
+    -- a TTL entry's expiry header.  Returns the segments and the first segments."""
+    k = table.setdefault((hdr.data_ptr(), 8 * hdr.numel()), len(table))
+    out, ofirst = [], [0]
+    for i in range(len(first) - 1):
+        out.append((k, 0, 8 * i, 8))
+        out.extend(segs[first[i]: first[i + 1]])
+        ofirst.append(len(out))
+    return out, ofirst
+
+
 def _segments_to_device(segs, dev):
     import torch
     seg_arr = (Segment * max(len(segs), 1))(*segs)
@@ -1076,6 +1148,28 @@ class ScatterResult:
         if bad:
             raise ValueError(f"the segments of queries {bad[:8]} do not hold exactly their payloads' bytes")
         return [True if s == GATHER_OK else False if s == GATHER_BAD_CRC else None for s in self.status]
+
+
+class TtlReadResult:
+    """What a batched read_with_ttl decided for n keys: the host arrays `status`
+    (TTL_NOT_FOUND / _LIVE / _EXPIRED / _TOO_SHORT) and `expiry` (the stored
+    expiry for LIVE and EXPIRED, else 0), `n_evicted` (tombstones the call wrote)
+    and `gather`: the GatherResult of the live payloads, expiry header included
+    (batch_read_with_ttl), or the ScatterResult (batch_read_with_ttl_into)."""
+
+    def __init__(self, status, expiry, gather):
+        self.status, self.expiry, self.gather, self.n_evicted = status, expiry, gather, 0
+
+    def __len__(self):
+        return len(self.status)
+
+    def is_valid_checksum(self):
+        """EntryHandle::is_valid_checksum per key: [bool | None] (None: not LIVE, nothing was read)."""
+        return self.gather.is_valid_checksum()
+
+    def values(self):
+        """[value bytes | None] in key order (None: not LIVE): the gathered payloads without their 8 expiry bytes."""
+        return [p[8:] if s == TTL_LIVE and p is not None else None for s, p in zip(self.status, self.gather.payloads())]
 
 
 def payload_scatter_device(d_file: int, file_len: int, d_start: int, d_end: int, n: int, dst_ptrs, dst_lens,
@@ -1587,13 +1681,19 @@ class DeviceStore:
         n = len(entries)
         if not n:
             return self._tail
-        dev = self.buf.device
-        srcs, segs, first, keep = _segment_table(entries, dev)
+        srcs, segs, first, keep = _segment_table(entries, self.buf.device)
+        return self._append_segments(hashes, srcs, segs, first, keep)
+
+    def _append_segments(self, hashes, srcs, segs, first, _keep) -> int:
+        """srd_batch_append_segments_device over a source table, its srd_segment
+        tuples and the entries' first segments (_segment_table's), reindex, tail."""
+        import torch
+        dev, n = self.buf.device, len(first) - 1
         d_segs = _segments_to_device(segs, dev)
         d_first = self.index._as_dev(np.array(first, np.uint64))
         d_hashes = self.index._as_dev(hashes)
         d_mo = torch.empty(n, dtype=torch.int64, device=dev)
-        return self._append_reindex(  # (keep holds the segments until the call has returned)
+        return self._append_reindex(  # (_keep holds the segments until the call has returned)
             lambda: batch_append_segments_device([p for p, _ in srcs], [nb for _, nb in srcs], d_segs.data_ptr(),
                                                  len(segs), d_first.data_ptr(), d_hashes.data_ptr(), n, self._tail,
                                                  self.buf.data_ptr(), self.buf.numel(), d_mo.data_ptr(), self.ctx),
@@ -1821,6 +1921,170 @@ class DeviceStore:
         """iter_entries (data_store.rs:276-280) over the live index: numpy arrays
         (start, end, meta_off, key_hash), newest first (EntryIterator order)."""
         return tuple(t.cpu().numpy().view(np.uint64) for t in self._live_entries())
+
+    # -- TTL entries (StorageCacheExt, extensions/src/storage_cache_ext.rs:23-107) ------------
+
+    def _ttl_hasher(self) -> NamespaceHasher:
+        if getattr(self, "_ttl_ns", None) is None:
+            self._ttl_ns = NamespaceHasher(TTL_PREFIX, self.ctx)
+        return self._ttl_ns
+
+    @staticmethod
+    def _ttl_expiries(n: int, ttl_secs, now) -> list[int]:
+        """now_secs.saturating_add(ttl_secs) (storage_cache_ext.rs:36-41), ttl_secs one number or one per key."""
+        now = int(time.time()) if now is None else int(now)
+        ttl = [int(ttl_secs)] * n if isinstance(ttl_secs, (int, np.integer)) else [int(t) for t in ttl_secs]
+        if len(ttl) != n:
+            raise ValueError("Mismatched lengths for keys and ttl_secs.")
+        if now < 0 or now > U64_MAX or any(t < 0 or t > U64_MAX for t in ttl):
+            raise ValueError("now and ttl_secs must fit an unsigned 64-bit integer")
+        return [min(now + t, U64_MAX) for t in ttl]
+
+    def batch_write_with_ttl(self, keys, values, ttl_secs, now=None) -> int:
+        """write_with_ttl (storage_cache_ext.rs:23-58) of every key: the payload
+        le64(expiry) || value (host bytes) under the hash of the key's namespaced
+        key, through batch_write_with_key_hashes.  Returns the new tail."""
+        _same_len(keys, values, "keys and values")
+        if not len(keys):
+            return self._tail
+        exp = self._ttl_expiries(len(keys), ttl_secs, now)
+        return self.batch_write_with_key_hashes(self._ttl_hasher().hash_batch(keys),
+                                                [e.to_bytes(8, "little") + bytes(v) for e, v in zip(exp, values)], False)
+
+    def write_with_ttl(self, key: bytes, value: bytes, ttl_secs: int, now=None) -> int:
+        return self.batch_write_with_ttl([key], [value], ttl_secs, now)
+
+    def batch_write_stream_with_ttl(self, keys, entries, ttl_secs, now=None) -> int:
+        """write_with_ttl for values that lie in HBM in pieces (entries[i]:
+        batch_write_stream_with_key_hashes' rule): the expiries are one device
+        uint64[n], entry i's first segment is its 8 bytes, the value's tensors
+        follow -- the segment append as it is.  Returns the new tail."""
+        import torch
+        _same_len(keys, entries, "keys and entries")
+        n = len(keys)
+        if not n:
+            return self._tail
+        dev = self.buf.device
+        exp = np.array(self._ttl_expiries(n, ttl_secs, now), np.uint64)
+        srcs, segs, first, keep = _segment_table(entries, dev)
+        d_exp = torch.from_numpy(exp.view(np.int64)).to(dev)
+        with_hdr, hfirst = _header_segments(srcs, segs, first, d_exp)
+        return self._append_segments(self._ttl_hasher().hash_batch(keys), srcs, with_hdr, hfirst, (keep, d_exp))
+
+    def _ttl_resolve(self, keys, now):
+        """srd_ttl_resolve_keys_device on the context stream: device tensors
+        (hashes, start, end, expiry, status, counts) and what must outlive the
+        caller's wait.  Nothing waits here."""
+        import torch
+        idx, dev = self.index, self.buf.device
+        kb, ko, kl = _blob(keys)
+        n = len(kl)
+        d_k, d_o, d_l = torch.from_numpy(kb.copy()).to(dev), idx._as_dev(ko), idx._as_dev(kl)
+        h, st, en, ex = (torch.empty(max(n, 1), dtype=torch.int64, device=dev) for _ in range(4))
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+        idx._lib_after_torch()
+        _check(lib().srd_ttl_resolve_keys_device(
+            self.ctx.h, C.c_void_p(idx.table.data_ptr()), idx.nbytes, C.c_void_p(self.buf.data_ptr()), self._tail,
+            self._ttl_hasher().prefix_hash, C.c_void_p(d_k.data_ptr()), C.c_void_p(d_o.data_ptr()),
+            C.c_void_p(d_l.data_ptr()), n, now, C.c_void_p(h.data_ptr()), C.c_void_p(st.data_ptr()),
+            C.c_void_p(en.data_ptr()), C.c_void_p(ex.data_ptr()), C.c_void_p(status.data_ptr()),
+            C.c_void_p(counts.data_ptr()), C.c_void_p(self.ctx.stream)))
+        return h[:n], st[:n], en[:n], ex[:n], status[:n], counts, (d_k, d_o, d_l)
+
+    def _ttl_evict(self, d_hashes, d_status) -> int:
+        """srd_ttl_evict_device: the tombstones of the batch's expired keys, the
+        index and the tail.  Returns the number of keys evicted."""
+        idx = self.index
+        used, nt, nd = C.c_uint64(idx._used), C.c_uint64(), C.c_uint64()
+        rc = lib().srd_ttl_evict_device(self.ctx.h, C.c_void_p(idx.table.data_ptr()), idx.nbytes, C.byref(used),
+                                        C.c_void_p(d_hashes.data_ptr()), C.c_void_p(d_status.data_ptr()),
+                                        d_hashes.numel(), self._tail, C.c_void_p(self.buf.data_ptr()), self.buf.numel(),
+                                        C.byref(nt), C.byref(nd))  # synchronises
+        if rc == SRD_ERR_ARG and "file_cap" in lib().srd_last_error().decode():
+            raise ValueError("the tombstones end beyond the store's capacity")
+        _check(rc)
+        idx._used = int(used.value)
+        if idx._live is not None:
+            idx._live -= int(nd.value)  # (every evicted key was live: the resolve found it)
+        self._tail = int(nt.value)
+        return int(nd.value)
+
+    def batch_read_with_ttl(self, keys, now=None, evict: bool = True) -> "TtlReadResult":
+        """read_with_ttl (storage_cache_ext.rs:72-107) of every key at `now`: the
+        decision in one launch from the raw keys (srd_ttl_resolve_keys_device),
+        the live payloads gathered and checked (srd_payload_gather_device), and
+        -- unless evict=False -- one tombstone per distinct expired key
+        (srd_ttl_evict_device).  The batch is judged against the store as it is
+        when the call starts: an expired key listed twice is EXPIRED twice."""
+        now = int(time.time()) if now is None else int(now)
+        if not len(keys):
+            return TtlReadResult(np.zeros(0, np.uint8), np.zeros(0, np.uint64),
+                                 GatherResult(None, np.zeros(1, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint8),
+                                              np.zeros(0, np.uint32)))
+        h, st, en, ex, status, counts, _keep = self._ttl_resolve(keys, now)
+        g = gather_ranges(self.buf.data_ptr(), self._tail, st, en, 0, self.ctx)  # waits
+        res = TtlReadResult(status.cpu().numpy(), ex.cpu().numpy().view(np.uint64), g)
+        if evict and int(counts[TTL_EXPIRED]):
+            res.n_evicted = self._ttl_evict(h, status)
+        return res
+
+    def read_with_ttl(self, key: bytes, now=None):
+        """read_with_ttl (storage_cache_ext.rs:72-107): the value; None when expired (the entry is deleted);
+        KeyError when absent; ValueError("Data too short to contain TTL")."""
+        r = self.batch_read_with_ttl([key], now)
+        s = int(r.status[0])
+        if s == TTL_NOT_FOUND:
+            raise KeyError(f"Key not found: {key!r}")
+        if s == TTL_TOO_SHORT:
+            raise ValueError("Data too short to contain TTL")
+        return r.values()[0] if s == TTL_LIVE else None
+
+    def batch_read_with_ttl_into(self, keys, entries, now=None, evict: bool = True) -> "TtlReadResult":
+        """batch_read_with_ttl with every live value read into the caller's own
+        tensors (entries[i]: batch_read_into's rule): the scatter with one internal
+        8-byte destination in front of each query's segments, which takes the
+        expiry header.  The result's gather is a ScatterResult."""
+        import torch
+        _same_len(keys, entries, "keys and entries")
+        now = int(time.time()) if now is None else int(now)
+        n, dev = len(keys), self.buf.device
+        if not n:
+            return TtlReadResult(np.zeros(0, np.uint8), np.zeros(0, np.uint64),
+                                 ScatterResult(np.zeros(0, np.uint8), np.zeros(0, np.uint32)))
+        srcs, segs, first, keep = _segment_table(entries, dev)
+        hdr = torch.empty(n, dtype=torch.int64, device=dev)
+        with_hdr, hfirst = _header_segments(srcs, segs, first, hdr)
+        h, st, en, ex, status, counts, _keep = self._ttl_resolve(keys, now)
+        sc = _scatter_table(self.buf.data_ptr(), self._tail, st, en, (srcs, with_hdr, hfirst, (keep, hdr)), self.ctx)
+        res = TtlReadResult(status.cpu().numpy(), ex.cpu().numpy().view(np.uint64), sc)
+        if evict and int(counts[TTL_EXPIRED]):
+            res.n_evicted = self._ttl_evict(h, status)
+        return res
+
+    def sweep_expired(self, now=None, plan: bool = False) -> TtlSweepStats:
+        """srd_ttl_sweep_device: every live entry judged as a TTL entry at `now`
+        (keys are not stored: for stores written only through the TTL writes),
+        the expired ones deleted -- tombstones in ascending offset of the entries
+        they remove; plan=True reports the counts and writes nothing.  Entries too
+        short to hold an expiry are left alone and counted.  `compact` then
+        returns the bytes."""
+        now = int(time.time()) if now is None else int(now)
+        idx = self.index
+        used, nt, st = C.c_uint64(idx._used), C.c_uint64(), TtlSweepStats()
+        idx._lib_after_torch()
+        rc = lib().srd_ttl_sweep_device(self.ctx.h, C.c_void_p(idx.table.data_ptr()), idx.nbytes, C.byref(used),
+                                        C.c_void_p(self.buf.data_ptr()), self._tail, self.buf.numel(), now,
+                                        TTL_SWEEP_PLAN if plan else 0, C.byref(nt), C.byref(st))  # synchronises
+        if rc == SRD_ERR_ARG and "file_cap" in lib().srd_last_error().decode():
+            raise ValueError("the tombstones end beyond the store's capacity")
+        _check(rc)
+        if not plan:
+            idx._used = int(used.value)
+            if int(nt.value) != self._tail:
+                idx._live = int(st.n_judged) - int(st.n_expired)
+            self._tail = int(nt.value)
+        return st
 
     # -- compaction and growth --------------------------------------------------------------
 

@@ -1,0 +1,329 @@
+// ASan/UBSan check of the TTL cache's rule (TEST INFRASTRUCTURE):
+// rust-simd-r-drive_amd/csrc/srd_ttl.h and srd_table.h compiled for the host --
+// entry_range, ttl_judge, ttl_expiry and eviction's choice as the kernels run
+// them -- against stores built here byte by byte in heap buffers of exactly
+// file_len bytes (ASan's redzones are the guards: a read at file_len or below
+// the buffer is a report) and a model written from the contract:
+//   - ttl_judge over seeded random stores (values of 0 .. 200 bytes, expiries
+//     around `now`, tombstones, plain entries below 8 bytes), every entry, at
+//     every truncation of the store that still holds the entry's metadata and
+//     at those that do not: the model's status, range and expiry, and no read
+//     outside [0, file_len);
+//   - the boundaries expiry = now - 1, now, now + 1, 0, 2^64 - 1, with now = 0
+//     and now = 2^64 - 1 too;
+//   - payload lengths 1, 7, 8 (an empty value), 9;
+//   - a tombstone (at offset 0 and behind an entry), an offset out of range,
+//     an offset whose 20 bytes end one past file_len, a metadata record ending
+//     exactly at file_len, prev_offset values near 2^64;
+//   - ttl_expiry saturates;
+//   - the resolve's path through the table (table_get, then ttl_judge): absent
+//     and removed keys are NOT_FOUND without a read of the store;
+//   - eviction's order: over seeded batches with repeated keys and mixed
+//     statuses, the candidates packed in batch order and deduplicated through a
+//     scratch table of 1 + last position per key (live_dedupe_kernel's rule, run
+//     serially) give one tombstone per distinct expired key, in batch order of
+//     each key's last expired query, at tail + 21 * rank.
+// Exit status 0 = no sanitizer report and every check held.
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <map>
+#include <vector>
+
+#include "srd_table.h"
+#include "srd_ttl.h"
+
+using namespace srd;
+
+static int g_fail = 0;
+#define EXPECT(c)                                                                  \
+  do {                                                                             \
+    if (!(c)) {                                                                    \
+      if (g_fail < 20) fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #c); \
+      g_fail++;                                                                    \
+    }                                                                              \
+  } while (0)
+
+static uint64_t rng_state = 0x5EED0018ull;
+static uint64_t rnd() {  // splitmix64
+  uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+static void put64(std::vector<uint8_t>& f, uint64_t v) {
+  for (int k = 0; k < 8; k++) f.push_back((uint8_t)(v >> (8 * k)));
+}
+
+// what the model knows about an entry it wrote
+struct Ent {
+  uint64_t meta, start;  // metadata offset, payload start
+  bool tomb;
+};
+
+// the reference's append (data_store.rs:864-914): prepad to 64 (none for a
+// tombstone), payload, {key_hash, prev_offset = the tail before, crc}
+struct Store {
+  std::vector<uint8_t> f;
+  std::vector<Ent> ents;
+  void append(const std::vector<uint8_t>& payload, uint64_t kh, bool tomb) {
+    const uint64_t tail = f.size();
+    if (!tomb) f.resize(tail + ((64 - (tail & 63)) & 63), 0);
+    const uint64_t st = f.size();
+    f.insert(f.end(), payload.begin(), payload.end());
+    const uint64_t meta = f.size();
+    put64(f, kh);
+    put64(f, tail);
+    for (int k = 0; k < 4; k++) f.push_back((uint8_t)rnd());  // (the rule reads no checksum)
+    ents.push_back(Ent{meta, st, tomb});
+  }
+  void ttl(uint64_t expiry, uint64_t value_len, uint64_t kh) {
+    std::vector<uint8_t> p;
+    put64(p, expiry);
+    for (uint64_t i = 0; i < value_len; i++) p.push_back((uint8_t)rnd());
+    append(p, kh, false);
+  }
+  void plain(uint64_t len, uint64_t kh) {
+    std::vector<uint8_t> p;
+    for (uint64_t i = 0; i < len; i++) p.push_back((uint8_t)(rnd() | 1));
+    append(p, kh, false);
+  }
+  void tombstone(uint64_t kh) { append({0}, kh, true); }
+};
+
+// ttl_judge on an exact-size heap copy of f[0 .. flen)
+static TtlVerdict judge_at(const std::vector<uint8_t>& f, uint64_t flen, uint64_t off, uint64_t now) {
+  uint8_t* buf = new uint8_t[flen ? flen : 1];
+  if (flen) memcpy(buf, f.data(), flen);
+  const TtlVerdict v = ttl_judge(flen ? buf : nullptr, flen, off, now);
+  delete[] buf;
+  return v;
+}
+
+static TtlVerdict model(const Store& s, const Ent& e, uint64_t flen, uint64_t now) {
+  TtlVerdict v{TTL_NOT_FOUND, 0, 0, 0};
+  if (e.meta + 20 > flen || e.tomb) return v;
+  if (e.meta - e.start < 8) { v.status = TTL_TOO_SHORT; return v; }
+  uint64_t x = 0;
+  for (int k = 0; k < 8; k++) x |= (uint64_t)s.f[e.start + k] << (8 * k);
+  v.expiry = x;
+  if (now >= x) { v.status = TTL_EXPIRED; return v; }
+  v.status = TTL_LIVE;
+  v.start = e.start;
+  v.end = e.meta;
+  return v;
+}
+
+static bool same(const TtlVerdict& a, const TtlVerdict& b) {
+  return a.status == b.status && a.start == b.start && a.end == b.end && a.expiry == b.expiry;
+}
+
+static void check_store(const Store& s, uint64_t now) {
+  for (const Ent& e : s.ents) {
+    const uint64_t lens[] = {s.f.size(), e.meta + 20, e.meta + 19, e.meta + 8, e.meta, 0};
+    for (uint64_t flen : lens) {
+      if (flen > s.f.size()) continue;
+      EXPECT(same(judge_at(s.f, flen, e.meta, now), model(s, e, flen, now)));
+    }
+  }
+}
+
+static void random_stores() {
+  const uint64_t now = 1700000000ull;
+  for (int round = 0; round < 40; round++) {
+    Store s;
+    const int n = 1 + (int)(rnd() % 40);
+    for (int i = 0; i < n; i++) {
+      const uint64_t r = rnd() % 10;
+      if (r == 0) s.tombstone(rnd());
+      else if (r == 1) s.plain(1 + rnd() % 7, rnd());
+      else s.ttl(now - 3 + rnd() % 7, rnd() % 200, rnd());
+    }
+    check_store(s, now);
+    // offsets that are no entry's: in range, at the end, far outside
+    for (int k = 0; k < 50; k++) judge_at(s.f, s.f.size(), rnd() % (s.f.size() + 40), now);
+    EXPECT(judge_at(s.f, s.f.size(), s.f.size(), now).status == TTL_NOT_FOUND);
+    EXPECT(judge_at(s.f, s.f.size(), ~0ull - 30, now).status == TTL_NOT_FOUND);
+    EXPECT(judge_at(s.f, s.f.size(), (1ull << 48) - 1, now).status == TTL_NOT_FOUND);
+  }
+}
+
+static void boundaries() {
+  const uint64_t nows[] = {0, 1, 1700000000ull, ~0ull - 1, ~0ull};
+  for (uint64_t now : nows) {
+    Store s;
+    const uint64_t exps[] = {now - 1, now, now + 1, 0, ~0ull};
+    for (uint64_t x : exps) s.ttl(x, 5, rnd());
+    for (size_t i = 0; i < 5; i++) {
+      const TtlVerdict v = judge_at(s.f, s.f.size(), s.ents[i].meta, now);
+      const uint64_t x = exps[i];
+      EXPECT(v.expiry == x);
+      EXPECT(v.status == (now >= x ? TTL_EXPIRED : TTL_LIVE));
+      if (v.status == TTL_LIVE) EXPECT(v.start == s.ents[i].start && v.end == s.ents[i].meta && v.end - v.start == 13);
+      else EXPECT(v.start == 0 && v.end == 0);
+    }
+    check_store(s, now);
+  }
+  // expiry == now is expired, now + 1 is live (away from the wrap)
+  {
+    Store s;
+    s.ttl(1000, 0, 1);
+    EXPECT(judge_at(s.f, s.f.size(), s.ents[0].meta, 999).status == TTL_LIVE);
+    EXPECT(judge_at(s.f, s.f.size(), s.ents[0].meta, 1000).status == TTL_EXPIRED);
+    EXPECT(judge_at(s.f, s.f.size(), s.ents[0].meta, 1001).status == TTL_EXPIRED);
+  }
+}
+
+static void lengths() {
+  const uint64_t now = 50;
+  Store s;
+  s.plain(1, 1);  // (a single non-zero byte: not a tombstone)
+  s.plain(7, 2);
+  s.ttl(100, 0, 3);  // 8 bytes: an empty value
+  s.ttl(100, 1, 4);  // 9
+  const uint32_t want[] = {TTL_TOO_SHORT, TTL_TOO_SHORT, TTL_LIVE, TTL_LIVE};
+  for (int i = 0; i < 4; i++) {
+    const TtlVerdict v = judge_at(s.f, s.f.size(), s.ents[i].meta, now);
+    EXPECT(v.status == want[i]);
+    if (want[i] == TTL_TOO_SHORT) EXPECT(v.start == 0 && v.end == 0 && v.expiry == 0);
+  }
+  EXPECT(judge_at(s.f, s.f.size(), s.ents[2].meta, now).end - judge_at(s.f, s.f.size(), s.ents[2].meta, now).start == 8);
+  EXPECT(judge_at(s.f, s.f.size(), s.ents[3].meta, now).end - judge_at(s.f, s.f.size(), s.ents[3].meta, now).start == 9);
+  // the last record ends exactly at file_len; one byte less and it is out of range
+  EXPECT(s.ents[3].meta + 20 == s.f.size());
+  EXPECT(judge_at(s.f, s.f.size() - 1, s.ents[3].meta, now).status == TTL_NOT_FOUND);
+  check_store(s, now);
+}
+
+static void tombstones_and_ranges() {
+  const uint64_t now = 50;
+  {
+    Store s;
+    s.tombstone(9);  // at offset 0: prev_offset 0, the NULL byte at 0, metadata at 1
+    s.ttl(100, 3, 1);
+    s.tombstone(1);
+    EXPECT(s.ents[0].meta == 1);
+    for (const Ent& e : s.ents)
+      EXPECT(judge_at(s.f, s.f.size(), e.meta, now).status == (e.tomb ? TTL_NOT_FOUND : TTL_LIVE));
+    check_store(s, now);
+  }
+  // prev_offset values that no store holds: near 2^64, equal to and above the metadata offset
+  const uint64_t prevs[] = {~0ull, ~0ull - 62, ~0ull - 63, 1ull << 63, 64, 65, 84, 1000};
+  for (uint64_t prev : prevs) {
+    Store s;
+    s.ttl(100, 3, 1);
+    const uint64_t meta = s.ents[0].meta;
+    for (int k = 0; k < 8; k++) s.f[meta + 8 + k] = (uint8_t)(prev >> (8 * k));
+    const TtlVerdict v = judge_at(s.f, s.f.size(), meta, now);
+    // in range only if the implied start lies below the metadata; never a read outside (ASan)
+    const uint64_t st = prev + ((64 - (prev & 63)) & 63);
+    if (st >= meta) EXPECT(v.status == TTL_NOT_FOUND);
+    else EXPECT(v.status != TTL_NOT_FOUND);
+  }
+}
+
+static void expiry_add() {
+  EXPECT(ttl_expiry(0, 0) == 0);
+  EXPECT(ttl_expiry(1700000000ull, 60) == 1700000060ull);
+  EXPECT(ttl_expiry(~0ull, 0) == ~0ull);
+  EXPECT(ttl_expiry(~0ull, 1) == ~0ull);
+  EXPECT(ttl_expiry(~0ull - 5, 5) == ~0ull);
+  EXPECT(ttl_expiry(~0ull - 5, 6) == ~0ull);
+  EXPECT(ttl_expiry(1, ~0ull) == ~0ull);
+  EXPECT(ttl_expiry(1ull << 63, 1ull << 63) == ~0ull);
+}
+
+// the resolve's per-query path on a host table
+static void through_the_table() {
+  const uint64_t now = 1000;
+  Store s;
+  std::vector<uint64_t> mem(table_bytes_for(8) / 8);
+  Table t = table_view(mem.data(), mem.size() * 8);
+  for (uint64_t i = 0; i < (1ull << t.log2cap); i++) t.packed[i] = TBL_EMPTY;
+  const uint64_t exps[] = {999, 1000, 1001, 5000};
+  for (uint64_t k = 0; k < 4; k++) {
+    const uint64_t kh = rnd();
+    s.ttl(exps[k], 10 + k, kh);
+    table_claim(t, kh, (kh >> 48 << 48) | s.ents.back().meta);
+  }
+  // one key removed: its slot keeps the key, the packed word is TBL_DELETED
+  uint64_t slot;
+  const uint64_t removed = ld_u64_unaligned(s.f.data(), s.ents[3].meta);
+  EXPECT(table_find(t, removed, &slot) != TBL_EMPTY);
+  t.packed[slot] = TBL_DELETED;
+  auto resolve = [&](uint64_t h) {
+    const uint64_t p = table_get(t, h);
+    TtlVerdict v{TTL_NOT_FOUND, 0, 0, 0};
+    if (p != TBL_EMPTY) v = judge_at(s.f, s.f.size(), p & 0xFFFFFFFFFFFFull, now);
+    return v;
+  };
+  EXPECT(resolve(ld_u64_unaligned(s.f.data(), s.ents[0].meta)).status == TTL_EXPIRED);
+  EXPECT(resolve(ld_u64_unaligned(s.f.data(), s.ents[1].meta)).status == TTL_EXPIRED);
+  EXPECT(resolve(ld_u64_unaligned(s.f.data(), s.ents[2].meta)).status == TTL_LIVE);
+  EXPECT(resolve(removed).status == TTL_NOT_FOUND);
+  EXPECT(resolve(rnd()).status == TTL_NOT_FOUND);
+}
+
+// eviction's order (srd_ttl_evict_device): candidates packed in batch order,
+// live_dedupe_kernel's scratch table over them run serially, the kept ones in
+// ascending position
+static void evict_order() {
+  for (int round = 0; round < 200; round++) {
+    const uint64_t n = 1 + rnd() % 300, nkeys = 1 + rnd() % 40;
+    std::vector<uint64_t> keys(nkeys), q(n);
+    std::vector<uint32_t> status(n);
+    for (auto& k : keys) k = round % 3 ? rnd() : rnd() % 4 + (~0ull - 1);  // (0 and 2^64 - 1 are legal hashes)
+    for (uint64_t i = 0; i < n; i++) {
+      q[i] = keys[rnd() % nkeys];
+      status[i] = (uint32_t)(rnd() % 4);
+    }
+    // the code's way
+    std::vector<uint64_t> xq;
+    for (uint64_t i = 0; i < n; i++)
+      if (ttl_evict_candidate(status[i])) xq.push_back(q[i]);
+    const uint64_t m = xq.size();
+    uint32_t log2dc = 6;
+    while ((1ull << log2dc) < 2 * m) log2dc++;
+    std::vector<uint32_t> dslot(1ull << log2dc, 0), lslot(m);
+    const uint32_t mask = (1u << log2dc) - 1;
+    for (uint64_t j = 0; j < m; j++) {
+      uint32_t s = (uint32_t)idx_slot(xq[j], log2dc);
+      while (dslot[s] && xq[dslot[s] - 1] != xq[j]) s = (s + 1) & mask;
+      if (dslot[s] < j + 1) dslot[s] = (uint32_t)j + 1;
+      lslot[j] = s;
+    }
+    std::vector<uint64_t> tombs;
+    for (uint64_t j = 0; j < m; j++)
+      if (ttl_evict_keeps(dslot[lslot[j]], j)) tombs.push_back(xq[j]);
+    // the contract's way: each distinct key with an EXPIRED query, ordered by its last such query
+    std::map<uint64_t, uint64_t> last;
+    for (uint64_t i = 0; i < n; i++)
+      if (status[i] == TTL_EXPIRED) last[q[i]] = i;
+    std::map<uint64_t, uint64_t> by_pos;
+    for (auto& kv : last) by_pos[kv.second] = kv.first;
+    std::vector<uint64_t> want;
+    for (auto& kv : by_pos) want.push_back(kv.second);
+    EXPECT(tombs == want);
+  }
+  EXPECT(ttl_evict_candidate(TTL_EXPIRED) && !ttl_evict_candidate(TTL_LIVE) && !ttl_evict_candidate(TTL_NOT_FOUND) &&
+         !ttl_evict_candidate(TTL_TOO_SHORT) && !ttl_evict_candidate(77));
+}
+
+int main() {
+  EXPECT(TTL_NOT_FOUND == 0 && TTL_LIVE == 1 && TTL_EXPIRED == 2 && TTL_TOO_SHORT == 3 && TTL_HEADER == 8);
+  random_stores();
+  boundaries();
+  lengths();
+  tombstones_and_ranges();
+  expiry_add();
+  through_the_table();
+  evict_order();
+  if (g_fail) {
+    fprintf(stderr, "ttl_check: %d checks failed\n", g_fail);
+    return 1;
+  }
+  printf("ttl_check ok\n");
+  return 0;
+}
