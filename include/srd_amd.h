@@ -1025,6 +1025,75 @@ int srd_ttl_sweep_device(srd_ctx *ctx, void *d_table, uint64_t table_bytes, uint
                          uint8_t *d_file, uint64_t tail, uint64_t file_cap, uint64_t now,
                          uint32_t flags, uint64_t *new_tail, srd_ttl_sweep_stats *stats);
 
+/* ---- keyed reads into fixed-size rows, no host wait, graph-replayable ----
+ *   srd_read_rows_device <- batch_read_hashed_keys (data_store.rs:1111-1158)
+ *                           over read_entry_with_context (:502-565), each
+ *                           handle copied out (EntryHandle::as_slice) and
+ *                           checked (EntryHandle::is_valid_checksum,
+ *                           simd-r-drive-entry-handle/src/entry_handle.rs:260-275)
+ * "Fetch these n keys into my [n, row_stride] buffer": the look-up of
+ * srd_batch_read_hashed_device (d_hashes, the optional tag check against
+ * d_verify_hashes, file_len the bound no read crosses: an indexed offset at or
+ * above it is NONE) and the verified copy of srd_payload_gather_device in one
+ * call whose destination is known by arithmetic: query i's payload goes to
+ * d_out[i * row_stride ..).  d_status[i]:
+ *   SRD_GATHER_NONE     no such key, removed, tag mismatch, out of range or a
+ *                       tombstone: d_len[i] = 0, row i is not written;
+ *   SRD_ROWS_TOO_LONG   the payload is longer than row_cap: d_len[i] = its
+ *                       true length (the caller can fall back to a call with
+ *                       larger rows or to srd_payload_scatter_device), nothing
+ *                       of the entry is read but its metadata, row i is not
+ *                       written;
+ *   SRD_GATHER_OK       delivered, crc32(payload) == the stored checksum;
+ *   SRD_GATHER_BAD_CRC  delivered faithfully, the checksum differs;
+ * d_len[i] = the payload's length for the last two.  d_crc_computed[i]
+ * (nullable) = crc32(payload i), 0 unless delivered.  d_counts (nullable, 6
+ * words) is SET to the number of queries per status value 0 .. 5 (3 and 4
+ * cannot arise here and stay 0).
+ * No byte outside [d_out + i * row_stride, d_out + i * row_stride + d_len[i])
+ * of a delivered row is written: no padding, no zero fill (the scatter's rule,
+ * not the gather's).  Of a payload nothing outside [start, end) is read, plus
+ * its metadata.
+ * SRD_ERR_ARG, decided on the host by arithmetic with nothing enqueued: d_out
+ * not 16-byte aligned; row_stride not a multiple of 16, or below row_cap;
+ * row_cap == 0; n >= 2^31; n * ceil(row_cap / SRD_GATHER_CHUNK) >= 2^32 (the
+ * bound on the work units); n * row_stride not fitting 64 bits; [d_out, d_out
+ * + n * row_stride) meeting d_file[0 .. srd_padded_size(file_len)); flags != 0;
+ * a NULL among the required pointers with n > 0.  n == 0 runs nothing.
+ * Ordered on `stream`.  The call DOES NOT WAIT: it reads nothing back, waits
+ * for nothing, allocates and frees nothing and makes no synchronous copy once
+ * the workspace for (n, row_cap) is there -- after srd_ctx_reserve_rows(ctx, n,
+ * row_cap) or any earlier call of at least that n and row_cap -- and returns
+ * with everything enqueued: later work on `stream` sees d_out and the output
+ * arrays.  So the call can be captured into a graph (hipStreamBeginCapture)
+ * and replayed: a replay reads the table, the store and d_hashes as they are
+ * then, and is valid while d_table, d_file, the caller's arrays and the
+ * workspace are where they were.  If `stream` is capturing and the workspace
+ * would have to grow, the call returns SRD_ERR_ARG with a message that names
+ * srd_ctx_reserve_rows, before anything is enqueued; outside a capture it
+ * grows the workspace as every other entry does (and may wait doing so).  The
+ * workspace is this entry's own: no other entry moves it.  One call (or
+ * replay) per context may be in flight at a time unless all of them are
+ * ordered on one stream.
+ *
+ * srd_ctx_reserve_rows: the workspace for every later srd_read_rows_device of
+ * at most n queries and at most row_cap bytes per row, so that those calls do
+ * not wait and can be captured.  What the reserve is for is exactly that; it
+ * may synchronise the device, and it moves the workspace when it grows it
+ * (which ends the validity of graphs captured before).  SRD_ERR_ARG: n >=
+ * 2^31 or a unit bound of 2^32 or more.  srd_ctx_device_bytes counts the
+ * workspace. */
+#define SRD_ROWS_TOO_LONG 5u /* d_status: the payload is longer than row_cap; d_len holds its length */
+int srd_ctx_reserve_rows(srd_ctx *ctx, uint64_t n, uint64_t row_cap);
+int srd_read_rows_device(srd_ctx *ctx, const void *d_table, uint64_t table_bytes,
+                         const uint8_t *d_file, uint64_t file_len,
+                         const uint64_t *d_hashes, const uint64_t *d_verify_hashes /* nullable */,
+                         uint64_t n, uint8_t *d_out, uint64_t row_stride, uint64_t row_cap,
+                         uint64_t *d_len /* n */, uint8_t *d_status /* n */,
+                         uint32_t *d_crc_computed /* n, nullable */,
+                         uint64_t *d_counts /* 6, by status value, nullable */,
+                         uint32_t flags /* 0 */, void *stream);
+
 /* Synthetic store of the BASELINE configs written on the device (the
  * checksum-on-append writer of data_store.rs:847-939 for keys
  * "bench-key-{i}" and counter-mode splitmix64 payloads).  lens==NULL ->

@@ -37,6 +37,11 @@
 //     srd_index.hip           lookup table build and reads, iterator, compaction
 //     srd_index_live.hip      the table kept live: apply, export, batched delete; the live compaction's two steps
 //     srd_ttl.hip             the TTL cache: namespaced key hash, the batched read's decision, the sweep
+//     srd_rows.h              the rows read's rule: a looked-up entry's status, length and unit count (rows_judge),
+//                             the unit bound that sizes grids and workspace, the host's refusals (a CPU check uses
+//                             it too)
+//     srd_rows.hip            keyed reads into fixed-size rows with no host wait: layout (look-up included) and
+//                             finish around the unit kernels' device-count forms
 //     srd_probe.hip           stream probe
 //   host code (in include order: each file uses only the ones above it)
 //     srd_host.cpp / .h       no-HIP parsers (shard cuts, batch layout)
@@ -50,7 +55,7 @@
 //     srd_multi.hip           multi-GPU open
 //     srd_ops.hip             probe, batch digests, synth, writer, table / reads / maintenance, iterator,
 //                             compaction, payload gather and scatter, device append, segment append, live
-//                             compaction, TTL cache
+//                             compaction, TTL cache, rows read
 //   this file               error / build-info entries, stamps read-outs, host self-test
 //
 // Glue scans/compactions use hipCUB (library primitives, like calling
@@ -93,6 +98,8 @@
 #include "srd_index.hip"
 #include "srd_index_live.hip"
 #include "srd_ttl.hip"
+#include "srd_rows.h"
+#include "srd_rows.hip"
 #include "srd_probe.hip"
 
 using namespace srd;

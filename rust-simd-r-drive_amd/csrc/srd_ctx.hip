@@ -242,6 +242,9 @@ enum BufId {
   B_CL_XK, B_CL_XP, B_CL_LEN, B_CL_MO, B_CL_PACKED, B_CL_CNT,  // live compaction (on top of the export's, the iterator's and the append's)
   B_SG_SRC, B_SG_LEN, B_SG_OFF, B_SG_UN, B_SG_UPRE, B_SG_ENT,  // segment append (on top of the append's)
   B_TT_CNT, B_TT_XQ, B_TT_FLAG, B_TT_POS,  // TTL eviction and sweep (on top of the delete's, the apply's and the export's)
+  // rows read (srd_read_rows_device): its own buffers, the scan's scratch included, which no other entry
+  // grows or moves -- a captured read holds their addresses
+  B_RW_START, B_RW_END, B_RW_EUN, B_RW_OFF, B_RW_UPRE, B_RW_CRC, B_RW_ST, B_RW_CNT, B_RW_UNIT, B_RW_RAW, B_RW_TMP,
   B_COUNT_
 };
 

@@ -1425,3 +1425,141 @@ extern "C" int srd_ttl_sweep_device(srd_ctx* c, void* d_table, uint64_t table_by
   // the flagged keys are distinct (a table's) and in ascending metadata offset already
   return tombs_commit(c, d_table, table_bytes, used, xk, flag, pos, nl, nk, tail, d_file, file_cap, new_tail);
 }
+
+// ---------------------------------------------------------------------------
+// Keyed reads into fixed-size rows (srd_rows.hip): the
+// look-up, the layout, the unit prefix, the unit kernels in their device-count
+// forms and the finish enqueued on the stream -- no count comes back to the
+// host.  Grids and workspace are sized from the bound on the units
+// (srd_rows.h); the workspace is the entry's own (B_RW_*), so a captured call
+// stays valid whatever the context's other entries grow.
+struct RowsBuf {
+  BufId id;
+  uint64_t bytes;
+};
+struct RowsWork {
+  uint64_t bound, per_row;
+  size_t scan_tmp;
+  RowsBuf need[11];
+};
+// (n < 2^31 and a bound below 2^32: rows_refusal's, or the reserve's own check)
+static int rows_work(uint64_t n, uint64_t row_cap, RowsWork* w) {
+  w->per_row = rows_units_per_row(row_cap);
+  w->bound = n * w->per_row;
+  w->scan_tmp = 0;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, w->scan_tmp, (const uint64_t*)nullptr, (uint64_t*)nullptr, n + 1));
+  const RowsBuf need[11] = {
+      {B_RW_START, rows_ws_u64(n)}, {B_RW_END, rows_ws_u64(n)},  {B_RW_EUN, rows_ws_u64(n)},
+      {B_RW_OFF, rows_ws_u64(n)},   {B_RW_UPRE, rows_ws_u64(n)}, {B_RW_CRC, rows_ws_u32(n)},
+      {B_RW_ST, rows_ws_u8(n)},     {B_RW_CNT, 64},              {B_RW_UNIT, rows_ws_units(w->bound)},
+      {B_RW_RAW, rows_ws_raw(w->bound)}, {B_RW_TMP, w->scan_tmp + 256}};
+  for (int k = 0; k < 11; k++) w->need[k] = need[k];
+  return 0;
+}
+static bool rows_work_ready(Ctx* c, const RowsWork& w) {
+  for (const auto& x : w.need)
+    if (!c->bufs[x.id].p || c->bufs[x.id].n < x.bytes) return false;
+  return true;
+}
+static int rows_work_grow(Ctx* c, const RowsWork& w) {
+  for (const auto& x : w.need) TRY(ensure(c, x.id, x.bytes));
+  (void)ttl_grid<rows_layout_kernel>(c, 1);  // (the runtime's occupancy answers: asked once, outside any capture)
+  (void)ttl_grid<rows_finish_kernel>(c, 1);
+  return 0;
+}
+
+extern "C" int srd_ctx_reserve_rows(srd_ctx* c, uint64_t n, uint64_t row_cap) {
+  uint64_t bound = 0;
+  if (!c || n >= (1ull << 31) || !rows_units_bound(n, row_cap, &bound) || bound >= (1ull << 32)) {
+    set_err("bad argument (n >= 2^31, or n * ceil(row_cap / SRD_GATHER_CHUNK) >= 2^32?)");
+    return SRD_ERR_ARG;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  RowsWork w;
+  TRY(rows_work(n, row_cap, &w));
+  if (rows_work_ready(c, w)) return 0;
+  // a buffer that is replaced may still be read by work on some stream
+  HIPCHK(hipDeviceSynchronize());
+  return rows_work_grow(c, w);
+}
+
+extern "C" int srd_read_rows_device(srd_ctx* c, const void* d_table, uint64_t table_bytes, const uint8_t* d_file,
+                                    uint64_t file_len, const uint64_t* d_hashes, const uint64_t* d_verify_hashes,
+                                    uint64_t n, uint8_t* d_out, uint64_t row_stride, uint64_t row_cap, uint64_t* d_len,
+                                    uint8_t* d_status, uint32_t* d_crc_computed, uint64_t* d_counts, uint32_t flags,
+                                    void* stream) {
+  if (!c) { set_err("bad argument"); return SRD_ERR_ARG; }
+  RowsCall rc{};
+  rc.file = (uint64_t)(uintptr_t)d_file;
+  rc.file_padded = d_file ? srd_padded_size(file_len) : 0;
+  rc.out = (uint64_t)(uintptr_t)d_out;
+  rc.n = n;
+  rc.row_stride = row_stride;
+  rc.row_cap = row_cap;
+  rc.flags = flags;
+  rc.ptrs = table_ok(d_table, table_bytes) && d_hashes && d_out && d_len && d_status && (d_file || !file_len);
+  if (const char* why = rows_refusal(rc)) { set_err(why); return SRD_ERR_ARG; }
+  if (!n) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream_of(c, stream);
+  RowsWork w;
+  TRY(rows_work(n, row_cap, &w));
+  if (!rows_work_ready(c, w)) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIPCHK(hipStreamIsCapturing(s, &cap));
+    if (cap != hipStreamCaptureStatusNone) {
+      set_err("the workspace for (n, row_cap) = (" + std::to_string(n) + ", " + std::to_string(row_cap) +
+              ") is not there and cannot grow while the stream is capturing: call srd_ctx_reserve_rows first");
+      return SRD_ERR_ARG;
+    }
+    TRY(rows_work_grow(c, w));
+  }
+  RowsArgs a{};
+  a.n = a.n_segs = n;
+  a.eun = P<uint64_t>(c, B_RW_EUN);
+  a.off = P<uint64_t>(c, B_RW_OFF);
+  a.upre = P<uint64_t>(c, B_RW_UPRE);
+  a.file = d_file;
+  a.start = a.o_start = P<uint64_t>(c, B_RW_START);
+  a.end = a.o_end = P<uint64_t>(c, B_RW_END);
+  a.unit = P<SegUnit>(c, B_RW_UNIT);
+  a.n_units = w.bound;
+  a.raw = P<uint32_t>(c, B_RW_RAW);
+  a.crc = P<uint32_t>(c, B_RW_CRC);
+  a.d_n_units = a.upre + n;
+  a.cnt = P<unsigned long long>(c, B_RW_CNT);
+  a.d_n_multi = a.cnt;
+  a.t = table_view(d_table, table_bytes);
+  a.flen = file_len;
+  a.q = d_hashes;
+  a.verify = d_verify_hashes;
+  a.row_stride = row_stride;
+  a.row_cap = row_cap;
+  a.st = P<uint8_t>(c, B_RW_ST);
+  a.o_len = d_len;
+  a.o_status = d_status;
+  a.o_crc = d_crc_computed;
+  a.o_counts = (unsigned long long*)d_counts;
+  rows_begin_kernel<<<1, 64, 0, s>>>(a.cnt, a.o_counts);
+  LAUNCHED(s, "rows_begin_kernel");
+  rows_layout_kernel<<<ttl_grid<rows_layout_kernel>(c, n + 1), 256, 0, s>>>(a);
+  LAUNCHED(s, "rows_layout_kernel");
+  size_t tb = c->bufs[B_RW_TMP].n;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(P<void>(c, B_RW_TMP), tb, (const uint64_t*)a.eun, a.upre, n + 1, s));
+  LAUNCHED(s, "hipcub");
+  units_kernel<RangeView, true><<<grid_for(w.bound), 256, 0, s>>>(a);
+  LAUNCHED(s, "units_kernel");
+  const unsigned g = (unsigned)std::min<uint64_t>((w.bound + SCAN_WAVES_V2 - 1) / SCAN_WAVES_V2, c->scan_blocks);
+  stream_copy_crc_kernel<false, true><<<g, SCAN_WAVES_V2 * 64, 0, s>>>(
+      StreamArgs{a.unit, w.bound, d_out, a.raw, a.crc, nullptr, a.d_n_units});
+  LAUNCHED(s, "stream_copy_crc_kernel");
+  if (w.per_row > 1) {  // (a row of one chunk at most has no multi-unit entry: known by arithmetic)
+    unit_terms_kernel<RangeView, true><<<grid_for(w.bound), 256, 0, s>>>(a);
+    LAUNCHED(s, "unit_terms_kernel");
+    unit_combine_kernel<RangeView, true><<<(unsigned)std::min<uint64_t>((n + 3) / 4, 4096), 256, 0, s>>>(a);
+    LAUNCHED(s, "unit_combine_kernel");
+  }
+  rows_finish_kernel<<<ttl_grid<rows_finish_kernel>(c, n), 256, 0, s>>>(a);
+  LAUNCHED(s, "rows_finish_kernel");
+  return 0;
+}

@@ -196,6 +196,11 @@ struct UnitArgs {
   uint64_t n_units;
   uint32_t* raw;   // [n_units] a multi-unit entry's units: crc_raw, then the unit's term
   uint32_t* crc;   // [n] an entry's CRC32
+  // the unit kernels' device-count forms (srd_read_rows_device): the unit count
+  // and the count of multi-unit entries are words in device memory, n_units
+  // above only bounds the grids
+  const uint64_t* d_n_units;
+  const unsigned long long* d_n_multi;
 };
 // (nothing is materialised for ranges: their unit count is eun[s], their unit
 // prefix upre[s], and the entry's first unit upre[i]); dst is where a

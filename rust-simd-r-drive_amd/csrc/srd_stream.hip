@@ -12,6 +12,7 @@ struct StreamArgs {
   uint32_t* raw;  // [n_units] a unit of a multi-unit entry: crc_raw
   uint32_t* crc;  // [entries] a single-unit entry's CRC32
   uint32_t* nz;   // [entries] NZ: set for an entry with a byte that is not 0
+  const uint64_t* d_n_units;  // DEV: the unit count, a word in device memory (n_units only bounds the grid)
 };
 
 // four destination words from two adjacent aligned source vectors w[0..8): the
@@ -57,9 +58,15 @@ __device__ __forceinline__ void seg_funnel(uint32_t (&d)[16], const uint32_t (&e
 // NZ (the stream rule): the unit also ORs its words, as write_kernel does for
 // its null_only word, and a unit with a byte that is not 0 marks its entry in
 // a.nz.
-template <bool NZ>
+// DEV (srd_read_rows_device): the unit count comes from device memory and the
+// grid from a bound, so whole blocks may have nothing to do: a block none of
+// whose waves has a unit leaves before the LDS fill (158 KiB per block; the
+// fill is a step of the whole block, so the decision is the block's).
+template <bool NZ, bool DEV = false>
 __global__ __launch_bounds__(SCAN_WAVES_V2 * 64, 1) void stream_copy_crc_kernel(StreamArgs a) {
   __shared__ ScanLds lds;
+  const uint64_t n_units = DEV ? *a.d_n_units : a.n_units;
+  if (DEV && (uint64_t)blockIdx.x * SCAN_WAVES_V2 >= n_units) return;
   load_crc_lds<true>(lds);
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -68,7 +75,7 @@ __global__ __launch_bounds__(SCAN_WAVES_V2 * 64, 1) void stream_copy_crc_kernel(
   const uint32_t nib_lane = lds_off(lds.nib) + 4u * (lane & 31);
   const uint64_t W = (uint64_t)gridDim.x * SCAN_WAVES_V2;
   const uint64_t w = (uint64_t)blockIdx.x * SCAN_WAVES_V2 + wv;
-  if (w >= a.n_units) return;
+  if (w >= n_units) return;
   const bool copy = a.out != nullptr;
   uint64_t last_len = ~0ull;  // cache of ~(x^(8 len) * 0xFFFFFFFF) for runs of equal lengths
   uint32_t last_fix = 0;
@@ -133,7 +140,7 @@ __global__ __launch_bounds__(SCAN_WAVES_V2 * 64, 1) void stream_copy_crc_kernel(
     if (b2 >= nb) {
       u2 = u + W;
       b2 = 0;
-      if (u2 < a.n_units) x2 = unit_s(u2);
+      if (u2 < n_units) x2 = unit_s(u2);
     }
     load_blk(x2, b2, nd, ne);
     bool vp[4];
@@ -216,7 +223,7 @@ __global__ __launch_bounds__(SCAN_WAVES_V2 * 64, 1) void stream_copy_crc_kernel(
     u = u2;
     b = b2;
     x = x2;
-    return u < a.n_units;
+    return u < n_units;
   };
   uint32_t c0[16], c1[16], n0[16], n1[16];
   load_blk(x, 0, c0, c1);

@@ -12,12 +12,16 @@
 //   unit_combine_kernel     one wave per multi-unit entry: the XOR of its
 //                           units' terms
 // (the last two only when the batch has a multi-unit entry)
+// DEV: the device-count forms (srd_read_rows_device, whose host never learns
+// the counts): the unit count is the word *a.d_n_units, the grids are sized
+// from a bound, and the last two leave at once when *a.d_n_multi is 0.
 
 namespace srd {
 
-template <class View>
+template <class View, bool DEV = false>
 __global__ __launch_bounds__(256) void units_kernel(UnitArgs a) {
-  for (uint64_t u = blockIdx.x * 256ull + threadIdx.x; u < a.n_units; u += gridDim.x * 256ull) a.unit[u] = unit_of<View>(a, u);
+  const uint64_t n_units = DEV ? *a.d_n_units : a.n_units;
+  for (uint64_t u = blockIdx.x * 256ull + threadIdx.x; u < n_units; u += gridDim.x * 256ull) a.unit[u] = unit_of<View>(a, u);
 }
 
 // The combine, in two steps (units of one entry have arbitrary lengths, so
@@ -25,9 +29,11 @@ __global__ __launch_bounds__(256) void units_kernel(UnitArgs a) {
 // the unit's raw CRC moved up by the entry's bytes behind the unit
 // (seg_unit_term: one x^(8 k) by square-and-multiply per unit, so one thread
 // per unit, not one wave per entry) -- in place of its raw CRC ...
-template <class View>
+template <class View, bool DEV = false>
 __global__ __launch_bounds__(256) void unit_terms_kernel(UnitArgs a) {
-  for (uint64_t u = blockIdx.x * 256ull + threadIdx.x; u < a.n_units; u += gridDim.x * 256ull) {
+  if (DEV && !*a.d_n_multi) return;
+  const uint64_t n_units = DEV ? *a.d_n_units : a.n_units;
+  for (uint64_t u = blockIdx.x * 256ull + threadIdx.x; u < n_units; u += gridDim.x * 256ull) {
     const SegUnit x = a.unit[u];
     if (!seg_lf_single(x.lf)) a.raw[u] = seg_unit_term(a.raw[u], View::ent_len(a, x.ent), x.end, g_tabs.pow8);
   }
@@ -35,8 +41,9 @@ __global__ __launch_bounds__(256) void unit_terms_kernel(UnitArgs a) {
 // ... then one wave per entry of more than one unit, the lanes striding over
 // the entry's units: the XOR of the terms is crc_raw(entry), and the
 // length-dependent init / xorout fix makes it the CRC32.
-template <class View>
+template <class View, bool DEV = false>
 __global__ __launch_bounds__(256) void unit_combine_kernel(UnitArgs a) {
+  if (DEV && !*a.d_n_multi) return;
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t W = gridDim.x * 4ull;
   for (uint64_t i = blockIdx.x * 4ull + (threadIdx.x >> 6); i < a.n; i += W) {

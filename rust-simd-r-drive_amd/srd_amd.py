@@ -76,6 +76,7 @@ EXPORTS = [
     "srd_batch_append_segments_device", "srd_payload_scatter_device",
     "srd_namespace_hash_batch_device", "srd_namespace_hash_batch", "srd_ttl_resolve_device",
     "srd_ttl_resolve_keys_device", "srd_ttl_evict_device", "srd_ttl_sweep_device",
+    "srd_ctx_reserve_rows", "srd_read_rows_device",
 ]
 
 
@@ -244,6 +245,8 @@ def lib():
                                            C.POINTER(u64)]
         L.srd_ttl_sweep_device.argtypes = [vp, vp, u64, C.POINTER(u64), vp, u64, u64, u64, u32, C.POINTER(u64),
                                            C.POINTER(TtlSweepStats)]
+        L.srd_ctx_reserve_rows.argtypes = [vp, u64, u64]
+        L.srd_read_rows_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, u64, u64, vp, vp, vp, vp, u32, vp]
         L.srd_iter_entries_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
         L.srd_estimate_compaction_savings_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.srd_compact_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, vp]
@@ -308,6 +311,12 @@ class Context:
     def set_timing_every(self, n: int):
         """With TIMING_SCAN: stamp only every n-th scan launch (srd_ctx_set_timing_every)."""
         _check(lib().srd_ctx_set_timing_every(self.h, n))
+
+    def reserve_rows(self, n: int, row_cap: int) -> None:
+        """srd_ctx_reserve_rows: the workspace for every later rows read of at most
+        n queries and row_cap bytes per row, so that those reads wait for nothing
+        and can be captured into a graph.  May synchronise."""
+        _check(lib().srd_ctx_reserve_rows(self.h, n, row_cap))
 
     def device_bytes(self) -> int:
         """srd_ctx_device_bytes: the context's device workspace (+ staging copy)."""
@@ -1150,6 +1159,61 @@ class ScatterResult:
         return [True if s == GATHER_OK else False if s == GATHER_BAD_CRC else None for s in self.status]
 
 
+# srd_read_rows_device (include/srd_amd.h): d_status holds GATHER_NONE / _OK / _BAD_CRC or
+ROWS_TOO_LONG = 5  # SRD_ROWS_TOO_LONG: the payload is longer than a row; lens holds its length
+
+
+class RowsResult:
+    """What srd_read_rows_device writes for n queries, as DEVICE tensors: `out`
+    ([n, row_cap] uint8: payload i in out[i, :lens[i]] when delivered, the row
+    left alone otherwise), `lens` (int64: the payload's length, also for a
+    ROWS_TOO_LONG row; 0 for no entry), `status` (uint8: GATHER_NONE / _OK /
+    _BAD_CRC, ROWS_TOO_LONG), `crc` (int32 bits of crc32(payload), 0 unless
+    delivered) and `counts` (int64[6], queries per status value; None unless
+    asked for).  Making one waits for nothing: the tensors are valid for work
+    ordered behind the read on the stream it ran on (`stream`).  The host
+    accessors below wait for that stream -- and torch's current one -- the first
+    time one of them is called, copy `status` and `lens` once and keep them; a
+    caller who replays a graph makes a new RowsResult of its tensors after each
+    replay."""
+
+    def __init__(self, out, lens, status, crc, counts=None, stream=None):
+        self.out, self.lens, self.status, self.crc, self.counts, self.stream = out, lens, status, crc, counts, stream
+        self._h = None
+
+    def _host(self):
+        if self._h is None:
+            import torch
+            if self.stream is not None:
+                self.stream.synchronize()
+            if self.status.is_cuda:
+                torch.cuda.current_stream(self.status.device).synchronize()
+            self._h = (self.status.cpu().numpy(), self.lens.cpu().numpy())
+        return self._h
+
+    def __len__(self):
+        return int(self.status.shape[0])
+
+    def is_valid_checksum(self):
+        """EntryHandle::is_valid_checksum per query: [bool | None] (None: nothing
+        was delivered -- no entry, or one too long for a row)."""
+        return [True if s == GATHER_OK else False if s == GATHER_BAD_CRC else None for s in self._host()[0]]
+
+    def too_long(self):
+        """[(query, true length)] of the ROWS_TOO_LONG rows: what to read again
+        with larger rows or through batch_read_into."""
+        st, ln = self._host()
+        return [(i, int(ln[i])) for i in np.flatnonzero(st == ROWS_TOO_LONG)]
+
+    def payloads(self):
+        """[payload bytes | None] in query order (None: nothing delivered), by one
+        copy of `out` to the host."""
+        st, ln = self._host()
+        rows = self.out.cpu().numpy() if len(st) else None
+        return [rows[i, : int(n)].tobytes() if s in (GATHER_OK, GATHER_BAD_CRC) else None
+                for i, (n, s) in enumerate(zip(ln, st))]
+
+
 class TtlReadResult:
     """What a batched read_with_ttl decided for n keys: the host arrays `status`
     (TTL_NOT_FOUND / _LIVE / _EXPIRED / _TOO_SHORT) and `expiry` (the stored
@@ -1424,6 +1488,64 @@ class DeviceIndex:
         _check(lib().srd_batch_read(self.ctx.h, C.c_void_p(self.table.data_ptr()), self.nbytes, C.c_void_p(d_file),
                                     file_len, _ptr(kb), _ptr(ko), _ptr(kl), n, _ptr(st), _ptr(en)))
         return [None if a == b else (int(a), int(b)) for a, b in zip(st[:n], en[:n])]
+
+    def read_rows(self, d_file: int, file_len: int, hashes, out, non_hashed_keys=None, lens=None, status=None,
+                  crc=None, counts=None) -> RowsResult:
+        """batch_read_hashed_keys (data_store.rs:1111-1158) with payload i copied
+        into row i of `out` and checked (srd_read_rows_device): the look-up, the
+        copy and the checksum on the device, with NO host wait anywhere -- nothing
+        of the layout goes through the host.  `out` is a 2-D uint8 tensor on the
+        index's device whose rows are contiguous (out.stride(1) == 1): row_cap =
+        out.shape[1], row_stride = out.stride(0), a multiple of 16, out.data_ptr()
+        16-byte aligned.  `hashes` may be a contiguous device int64 tensor, which is
+        used in place with no copy (a replayed graph reads it as it is then); a
+        host sequence is copied to the device first.  `non_hashed_keys` (host keys,
+        hashed here, which waits; or a device int64 tensor of their hashes, used in
+        place) verifies each read by tag_from_key (:513-521).  `lens` (int64[n]),
+        `status` (uint8[n]), `crc` (int32[n]) and `counts` (int64[6]) are the
+        caller's own output tensors when given -- a caller who replays a graph
+        passes them in; `counts` is only filled when given.  A row that is not
+        delivered (GATHER_NONE, ROWS_TOO_LONG) is left exactly as it was.
+        The stream rule: the call runs on torch's CURRENT stream.  Outside a
+        capture that stream first waits in-stream (an event) for the context
+        stream, so it sees what the library wrote before.  Under capture
+        (torch.cuda.is_current_stream_capturing()) no cross-stream wait is issued:
+        the caller has waited for the context stream (DeviceStore.sync) before
+        capturing, and has called Context.reserve_rows(n, row_cap) -- a capture
+        that would have to grow the workspace raises SrdError naming
+        srd_ctx_reserve_rows."""
+        import torch
+        dev = self.table.device
+        if not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.dim() == 2 and out.device == dev and
+                (out.shape[1] == 0 or out.stride(1) == 1)):
+            raise ValueError("out must be a 2-D uint8 tensor on the index's device with contiguous rows")
+        n = out.shape[0]
+        q = hashes if isinstance(hashes, torch.Tensor) else self._as_dev(hashes)
+        v = non_hashed_keys
+        if v is not None and not isinstance(v, torch.Tensor):
+            _same_len(v, q, "hashed and non-hashed keys")
+            v = self._as_dev(compute_hash_batch(v, self.ctx))
+        outs = {"hashes": (q, torch.int64, n), "non_hashed_keys": (v, torch.int64, n), "lens": (lens, torch.int64, n),
+                "status": (status, torch.uint8, n), "crc": (crc, torch.int32, n), "counts": (counts, torch.int64, 6)}
+        for name, (t, dt, m) in outs.items():
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dt and t.dim() == 1 and
+                                      t.numel() == m and t.device == dev and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of {m} elements on the index's device")
+        lens = lens if lens is not None else torch.empty(n, dtype=torch.int64, device=dev)
+        status = status if status is not None else torch.empty(n, dtype=torch.uint8, device=dev)
+        crc = crc if crc is not None else torch.empty(n, dtype=torch.int32, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        res = RowsResult(out, lens, status, crc, counts, cur)
+        if not n:
+            return res
+        if not torch.cuda.is_current_stream_capturing():
+            cur.wait_stream(torch.cuda.ExternalStream(self.ctx.stream, device=dev))
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _check(lib().srd_read_rows_device(self.ctx.h, p(self.table), self.nbytes, C.c_void_p(d_file), file_len, p(q), p(v),
+                                          n, p(out), out.stride(0), out.shape[1], p(lens), p(status), p(crc), p(counts), 0,
+                                          C.c_void_p(cur.cuda_stream)))
+        res._keep = (q, v)  # (temporaries of this call: torch's allocator reuses them in stream order)
+        return res
 
 
 # ---------------------------------------------------------------------------
@@ -1903,6 +2025,55 @@ class DeviceStore:
         """The batched is_valid_checksum of `keys` (no payload is copied):
         [True | False | None (no such key)] in query order."""
         return self.batch_gather(keys, GATHER_VERIFY_ONLY).is_valid_checksum()
+
+    # -- verified reads into fixed-size rows: no host wait, graph-replayable -------------------
+
+    def _rows_file_len(self) -> int:
+        """The buffer's capacity bound: the largest L with padded_size(L) <= buf.numel()."""
+        return max(self.buf.numel() // 4096 - 2, 0) * 4096
+
+    def batch_read_rows_hashed_keys(self, hashes, out, non_hashed_keys=None, **outs) -> RowsResult:
+        """batch_read_hashed_keys (data_store.rs:1111-1158) into the rows of `out`,
+        each payload checked (EntryHandle::is_valid_checksum): DeviceIndex.read_rows
+        over the session's buffer -- its contract, stream rule and keyword outputs
+        (lens, status, crc, counts) word for word.  No host wait happens anywhere in
+        the call when `hashes` (and `non_hashed_keys`, if given) are device tensors.
+        What is passed as the read bound is the buffer's CAPACITY bound (the
+        largest L with padded_size(L) <= buf.numel()), not the tail: the session's
+        index only ever points below the tail and no read leaves the buffer either
+        way, so the results are the same -- and a graph captured around this call
+        (after sync() and reserve_rows()) sees, when replayed, the entries appended
+        and deleted since.  A captured read is valid while rows_token() is
+        unchanged: DeviceIndex.grow, a write that grows the table, compact and
+        reserve move the table or the buffer (documented, not enforced)."""
+        return self.index.read_rows(self.buf.data_ptr(), self._rows_file_len(), hashes, out, non_hashed_keys, **outs)
+
+    def batch_read_rows(self, keys, out) -> RowsResult:
+        """batch_read (data_store.rs:1105-1109) into the rows of `out`:
+        compute_hash_batch of the host keys (which waits), then
+        batch_read_rows_hashed_keys with every read verified by its key's own tag."""
+        import torch
+        if len(keys) != out.shape[0]:
+            raise ValueError("Mismatched lengths for keys and rows.")
+        h = self.index._as_dev(compute_hash_batch(keys, self.ctx)) if len(keys) else \
+            torch.empty(0, dtype=torch.int64, device=self.buf.device)
+        return self.batch_read_rows_hashed_keys(h, out, h)
+
+    def reserve_rows(self, n: int, row_cap: int) -> None:
+        """Context.reserve_rows: the workspace for rows reads of at most n keys into
+        rows of at most row_cap bytes (what a capture needs beforehand)."""
+        self.ctx.reserve_rows(n, row_cap)
+
+    def sync(self) -> None:
+        """The host waits for the context stream: everything the session's writes
+        and deletes enqueued has landed (call it before capturing a rows read and
+        before replaying one after a write)."""
+        self.index._sync_lib()
+
+    def rows_token(self):
+        """(table ptr, table bytes, buffer ptr): a captured rows read is valid
+        while this is unchanged."""
+        return (self.index.table.data_ptr(), self.index.nbytes, self.buf.data_ptr())
 
     def iter_gather(self) -> GatherResult:
         """Every live payload in EntryIterator order (newest first), gathered and

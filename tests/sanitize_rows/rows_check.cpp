@@ -1,0 +1,291 @@
+// ASan/UBSan check of the rows read's rule (TEST INFRASTRUCTURE):
+// rust-simd-r-drive_amd/csrc/srd_rows.h over srd_ttl.h, srd_table.h and
+// srd_segments.h compiled for the host -- the per-query decision of
+// rows_layout_kernel (table_get, the tag check, entry_range, rows_judge), the
+// unit cut the unit kernels run under the range view, the host's refusals and
+// the workspace sizes -- against stores built here byte by byte in heap
+// buffers of exactly file_len bytes (ASan's redzones are the guards) and a
+// model written from the contract:
+//   - seeded random stores (payloads of 1 .. 300 bytes, tombstones), every key
+//     through a host table: present, absent, removed, tag mismatch, at every
+//     file_len around an entry's metadata (an offset at or above it is NONE);
+//   - rows_judge at row_cap = len - 1, len, len + 1 for len in 1, 15, 16, 17,
+//     63, 64, 65, C - 1, C, C + 1, 2 C + 5: delivered or TOO_LONG with the true
+//     length, the unit count gather_chunks(len);
+//   - for every delivered row the units unit_of<RangeView> gives with off[i] =
+//     i * stride tile [i * stride, i * stride + len_i) exactly, in order, none
+//     crossing into row i - 1 or i + 1, each reading only its own payload, at
+//     strides row_cap and row_cap + 16; the unit total is upre[n] of the
+//     exclusive sum over n + 1 counts; the total never exceeds rows_units_bound;
+//   - the refusals at 2^31, 2^32 and wrap-around values;
+//   - the workspace sizes are monotone in (n, row_cap).
+// Exit status 0 = no sanitizer report and every check held.
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "srd_table.h"
+#include "srd_ttl.h"
+#include "srd_rows.h"
+
+using namespace srd;
+
+static int g_fail = 0;
+#define EXPECT(c)                                                                  \
+  do {                                                                             \
+    if (!(c)) {                                                                    \
+      if (g_fail < 20) fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #c); \
+      g_fail++;                                                                    \
+    }                                                                              \
+  } while (0)
+
+static uint64_t rng_state = 0x5EED0019ull;
+static uint64_t rnd() {  // splitmix64
+  uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+static void put64(std::vector<uint8_t>& f, uint64_t v) {
+  for (int k = 0; k < 8; k++) f.push_back((uint8_t)(v >> (8 * k)));
+}
+
+struct Ent {
+  uint64_t kh, meta, start;
+  bool tomb;
+};
+// the reference's append (data_store.rs:864-914): prepad to 64 (none for a
+// tombstone), payload, {key_hash, prev_offset = the tail before, crc}
+struct Store {
+  std::vector<uint8_t> f;
+  std::vector<Ent> ents;
+  void append(uint64_t len, uint64_t kh, bool tomb) {
+    const uint64_t tail = f.size();
+    if (!tomb) f.resize(tail + ((64 - (tail & 63)) & 63), 0);
+    const uint64_t st = f.size();
+    for (uint64_t i = 0; i < len; i++) f.push_back(tomb ? 0 : (uint8_t)(rnd() | 1));
+    const uint64_t meta = f.size();
+    put64(f, kh);
+    put64(f, tail);
+    for (int k = 0; k < 4; k++) f.push_back((uint8_t)rnd());
+    ents.push_back(Ent{kh, meta, st, tomb});
+  }
+};
+
+// rows_layout_kernel's decision for one query, on an exact-size heap copy of f[0 .. flen)
+struct Row {
+  RowVerdict v;
+  uint64_t start, end;
+};
+static Row layout_at(const Table& t, const std::vector<uint8_t>& f, uint64_t flen, uint64_t q, const uint64_t* verify,
+                     uint64_t row_cap) {
+  uint8_t* buf = new uint8_t[flen ? flen : 1];
+  if (flen) memcpy(buf, f.data(), flen);
+  uint64_t start = 0, end = 0;
+  const uint64_t p = table_get(t, q);
+  bool have = p != TBL_EMPTY;
+  if (have && verify) have = (p >> 48) == (*verify >> 48);
+  if (have) have = entry_range(flen ? buf : nullptr, flen, p & 0xFFFFFFFFFFFFull, &start, &end);
+  const RowVerdict v = rows_judge(start, end, have, row_cap);
+  delete[] buf;
+  return Row{v, v.status == SRD_GATHER_NONE ? 0 : start, v.status == SRD_GATHER_NONE ? 0 : end};
+}
+
+static void random_stores() {
+  for (int round = 0; round < 30; round++) {
+    Store s;
+    const int n = 1 + (int)(rnd() % 40);
+    std::vector<uint64_t> mem(table_bytes_for(n) / 8);
+    Table t = table_view(mem.data(), mem.size() * 8);
+    for (uint64_t i = 0; i < (1ull << t.log2cap); i++) t.packed[i] = TBL_EMPTY;
+    for (int i = 0; i < n; i++) {
+      const uint64_t kh = rnd();
+      const bool tomb = rnd() % 8 == 0;
+      s.append(tomb ? 1 : 1 + rnd() % 300, kh, tomb);
+      table_claim(t, kh, (kh >> 48 << 48) | s.ents.back().meta);
+    }
+    // one key removed: its slot keeps the key, the packed word is TBL_DELETED
+    const size_t gone = rnd() % s.ents.size();
+    uint64_t slot;
+    EXPECT(table_find(t, s.ents[gone].kh, &slot) != TBL_EMPTY);
+    t.packed[slot] = TBL_DELETED;
+    const uint64_t row_cap = 1 + rnd() % 320;
+    for (size_t i = 0; i < s.ents.size(); i++) {
+      const Ent& e = s.ents[i];
+      const uint64_t len = e.meta - e.start;
+      const uint64_t flens[] = {s.f.size(), e.meta + 20, e.meta + 19, e.meta + 1, e.meta, 0};
+      for (uint64_t flen : flens) {
+        if (flen > s.f.size()) continue;
+        const Row r = layout_at(t, s.f, flen, e.kh, nullptr, row_cap);
+        if (i == gone || e.tomb || e.meta + 20 > flen) {  // removed, a tombstone, an offset at or above file_len
+          EXPECT(r.v.status == SRD_GATHER_NONE && r.v.len == 0 && r.v.units == 0 && r.start == 0 && r.end == 0);
+        } else if (len > row_cap) {
+          EXPECT(r.v.status == ROWS_TOO_LONG && r.v.len == len && r.v.units == 0 && r.end - r.start == len);
+        } else {
+          EXPECT(r.v.status == SRD_GATHER_OK && r.v.len == len && r.v.units == 1 && r.start == e.start && r.end == e.meta);
+        }
+      }
+      // the tag check: the key's own hash passes, one with another tag is NONE
+      const uint64_t same = e.kh, other = e.kh ^ (1ull << 50);
+      const Row a = layout_at(t, s.f, s.f.size(), e.kh, &same, row_cap), b = layout_at(t, s.f, s.f.size(), e.kh, &other, row_cap);
+      EXPECT(b.v.status == SRD_GATHER_NONE && b.v.len == 0);
+      EXPECT(a.v.status == layout_at(t, s.f, s.f.size(), e.kh, nullptr, row_cap).v.status);
+    }
+    EXPECT(layout_at(t, s.f, s.f.size(), rnd(), nullptr, row_cap).v.status == SRD_GATHER_NONE);  // absent
+  }
+}
+
+static const uint64_t C_ = GATHER_CHUNK;
+static const uint64_t kLens[] = {1, 15, 16, 17, 63, 64, 65, C_ - 1, C_, C_ + 1, 2 * C_ + 5};
+
+static void judge_boundaries() {
+  for (uint64_t len : kLens) {
+    const uint64_t starts[] = {0, 64, 1ull << 40};
+    for (uint64_t st : starts) {
+      for (uint64_t cap : {len - 1, len, len + 1}) {
+        const RowVerdict v = rows_judge(st, st + len, true, cap);
+        if (cap < len) EXPECT(v.status == ROWS_TOO_LONG && v.len == len && v.units == 0);
+        else EXPECT(v.status == SRD_GATHER_OK && v.len == len && v.units == (len + C_ - 1) / C_ && v.units <= rows_units_per_row(cap));
+      }
+      EXPECT(rows_judge(st, st + len, false, len).status == SRD_GATHER_NONE);
+    }
+  }
+  EXPECT(rows_judge(5, 5, true, 10).status == SRD_GATHER_NONE);
+  EXPECT(rows_judge(0, ~0ull, true, ~0ull).status == SRD_GATHER_OK);
+  EXPECT(rows_judge(0, ~0ull, true, ~0ull - 1).status == ROWS_TOO_LONG && rows_judge(0, ~0ull, true, 1).len == ~0ull);
+}
+
+// the batch of kLens as rows: the units of the range view tile each delivered row exactly
+static void unit_tiling() {
+  Store s;
+  for (uint64_t len : kLens) s.append(len, rnd(), false);
+  const uint64_t n = s.ents.size();
+  for (uint64_t row_cap : {(uint64_t)64, C_, C_ + 16, 2 * C_ + 5, 3 * C_ + 48}) {
+    for (uint64_t stride : {(row_cap + 15) & ~15ull, ((row_cap + 15) & ~15ull) + 16}) {
+      std::vector<uint64_t> start(n), end(n), eun(n + 1), off(n), upre(n + 1);
+      uint64_t total = 0;
+      for (uint64_t i = 0; i < n; i++) {
+        const RowVerdict v = rows_judge(s.ents[i].start, s.ents[i].meta, true, row_cap);
+        start[i] = s.ents[i].start;
+        end[i] = s.ents[i].meta;
+        eun[i] = v.units;
+        off[i] = i * stride;
+      }
+      eun[n] = 0;
+      for (uint64_t i = 0; i <= n; i++) { upre[i] = total; total += eun[i]; }
+      uint64_t bound = 0;
+      EXPECT(rows_units_bound(n, row_cap, &bound) && upre[n] <= bound);
+      UnitArgs a{};
+      a.n = a.n_segs = n;
+      a.eun = eun.data();
+      a.off = off.data();
+      a.upre = upre.data();
+      a.file = s.f.data();
+      a.start = start.data();
+      a.end = end.data();
+      a.dst0 = 0;
+      a.pad = false;
+      std::vector<uint64_t> next(n);  // where the next unit of row i must begin
+      for (uint64_t i = 0; i < n; i++) next[i] = i * stride;
+      for (uint64_t u = 0; u < upre[n]; u++) {
+        const SegUnit x = unit_of<RangeView>(a, u);
+        const uint64_t i = x.ent, len = end[i] - start[i], ul = seg_lf_len(x.lf);
+        EXPECT(i < n && eun[i] && upre[i] <= u && u < upre[i] + eun[i]);
+        EXPECT(x.dst == next[i] && ul >= 1 && ul <= C_);
+        EXPECT(x.dst >= i * stride && x.dst + ul <= i * stride + len);  // inside its own row's payload bytes
+        EXPECT(x.dst + ul <= i * stride + row_cap);
+        const uint64_t src0 = (uint64_t)(uintptr_t)s.f.data() + start[i];
+        EXPECT(x.src == src0 + (x.dst - i * stride) && x.src + ul <= src0 + len);
+        EXPECT(x.end == x.dst - i * stride + ul);
+        EXPECT(seg_lf_single(x.lf) == (eun[i] == 1) && seg_unit_pad(x.dst, x.lf) == 0);
+        const SegFrame f = seg_frame(x.src, x.dst, x.lf);
+        EXPECT(f.a == 0 && f.vlen == ul);  // a row starts at a 16-byte boundary and every chunk does
+        next[i] += ul;
+      }
+      for (uint64_t i = 0; i < n; i++) EXPECT(next[i] == i * stride + (eun[i] ? end[i] - start[i] : 0));
+    }
+  }
+}
+
+static const char* refuse(uint64_t file, uint64_t padded, uint64_t out, uint64_t n, uint64_t stride, uint64_t cap,
+                          uint32_t flags = 0, bool ptrs = true) {
+  RowsCall r{file, padded, out, n, stride, cap, flags, ptrs};
+  return rows_refusal(r);
+}
+static bool says(const char* m, const char* what) { return m && std::string(m).find(what) != std::string::npos; }
+
+static void refusals() {
+  const uint64_t F = 1ull << 30, P = 1ull << 20, O = 1ull << 32;
+  EXPECT(refuse(F, P, O, 4, 64, 64) == nullptr);
+  EXPECT(refuse(F, P, O, 0, 7, 0) == nullptr);  // n == 0 runs nothing
+  EXPECT(says(refuse(F, P, O, 0, 64, 64, 1), "flags"));
+  EXPECT(says(refuse(F, P, O, 4, 64, 64, 0, false), "NULL"));
+  EXPECT(says(refuse(F, P, O + 8, 4, 64, 64), "16-byte aligned"));
+  EXPECT(says(refuse(F, P, O, 4, 64, 0), "row_cap"));
+  EXPECT(says(refuse(F, P, O, 4, 72, 64), "multiple of 16"));
+  EXPECT(says(refuse(F, P, O, 4, 48, 64), "below row_cap"));
+  EXPECT(refuse(F, P, O, (1ull << 31) - 1, 16, 16) == nullptr);
+  EXPECT(says(refuse(F, P, O, 1ull << 31, 16, 16), "too many queries"));
+  EXPECT(says(refuse(F, P, O, ~0ull, 16, 16), "too many queries"));
+  // the unit bound: n * ceil(row_cap / C) at 2^32 and beyond, and where the product wraps
+  uint64_t b = 0;
+  EXPECT(rows_units_bound(1ull << 20, 4096, &b) && b == 1ull << 20);
+  EXPECT(rows_units_bound(64, 1ull << 20, &b) && b == 64 * 16);
+  EXPECT(rows_units_bound(3, C_ + 1, &b) && b == 6);
+  EXPECT(rows_units_bound(0, ~0ull, &b) && b == 0);
+  EXPECT(!rows_units_bound(1ull << 30, ~0ull, &b));
+  EXPECT(rows_units_per_row(~0ull) == (~0ull / C_) + 1 && rows_units_per_row(0) == 0 && rows_units_per_row(1) == 1);
+  const uint64_t big = C_ << 12;  // 4096 units per row
+  EXPECT(refuse(F, P, 1ull << 50, (1ull << 20) - 1, big, big) == nullptr);
+  EXPECT(says(refuse(F, P, 1ull << 50, 1ull << 20, big, big), "work units"));
+  EXPECT(says(refuse(F, P, O, 2, ~0ull & ~15ull, ~0ull & ~15ull), "work units"));
+  // n * row_stride wrapping, and rows that run off the address space
+  EXPECT(says(refuse(F, P, O, 1ull << 30, 1ull << 40, 16), "does not fit 64 bits"));
+  EXPECT(says(refuse(F, P, ~0ull & ~15ull, 2, 16, 16), "address space"));
+  EXPECT(refuse(F, P, (~0ull & ~15ull) - 32, 2, 16, 16) == nullptr);
+  // the store's padded range [F, F + P): touching, one byte in, around, inside
+  EXPECT(refuse(F, P, F - 4 * 64, 4, 64, 64) == nullptr);
+  EXPECT(says(refuse(F, P, F - 4 * 64 + 16, 4, 64, 64), "overlaps"));
+  EXPECT(says(refuse(F, P, F - 64, 1ull << 20, 64, 64), "overlaps"));
+  EXPECT(says(refuse(F, P, F + 4096, 4, 64, 64), "overlaps"));
+  EXPECT(says(refuse(F, P, F + P - 16, 4, 64, 64), "overlaps"));
+  EXPECT(refuse(F, P, F + P, 4, 64, 64) == nullptr);
+  EXPECT(refuse(0, 0, F, 4, 64, 64) == nullptr);  // (no store bytes: nothing to meet)
+}
+
+static void workspace_monotone() {
+  const uint64_t ns[] = {0, 1, 2, 63, 64, 65, 4096, 1ull << 20, (1ull << 31) - 1};
+  const uint64_t caps[] = {1, 16, 4096, C_ - 1, C_, C_ + 1, 3 * C_, 1ull << 20};
+  for (size_t i = 0; i + 1 < sizeof ns / 8; i++) {
+    EXPECT(rows_ws_u64(ns[i]) <= rows_ws_u64(ns[i + 1]) && rows_ws_u32(ns[i]) <= rows_ws_u32(ns[i + 1]) &&
+           rows_ws_u8(ns[i]) <= rows_ws_u8(ns[i + 1]));
+    EXPECT(rows_ws_u64(ns[i]) >= 8 * (ns[i] + 1));
+  }
+  for (size_t i = 0; i < sizeof ns / 8; i++)
+    for (size_t j = 0; j < sizeof caps / 8; j++) {
+      uint64_t b = 0, b2 = 0;
+      if (!rows_units_bound(ns[i], caps[j], &b)) continue;
+      if (i + 1 < sizeof ns / 8 && rows_units_bound(ns[i + 1], caps[j], &b2)) EXPECT(b <= b2);
+      if (j + 1 < sizeof caps / 8 && rows_units_bound(ns[i], caps[j + 1], &b2)) EXPECT(b <= b2);
+      if (b < (1ull << 32)) EXPECT(rows_ws_units(b) == 32 * b && rows_ws_raw(b) == 4 * b);
+    }
+}
+
+int main() {
+  EXPECT(ROWS_TOO_LONG == 5 && ROWS_STATUSES == 6);
+  random_stores();
+  judge_boundaries();
+  unit_tiling();
+  refusals();
+  workspace_monotone();
+  if (g_fail) {
+    fprintf(stderr, "rows_check: %d checks failed\n", g_fail);
+    return 1;
+  }
+  printf("rows_check ok\n");
+  return 0;
+}
