@@ -19,19 +19,11 @@
 #include <random>
 #include <vector>
 
+#include "check.h"
 #include "srd_append.h"
 #include "srd_host.h"
 
 using namespace srd;
-
-static int g_fail = 0;
-#define EXPECT(c)                                                                  \
-  do {                                                                             \
-    if (!(c)) {                                                                    \
-      if (g_fail < 20) fprintf(stderr, "%s:%d: invariant failed: %s\n", __FILE__, __LINE__, #c); \
-      g_fail++;                                                                    \
-    }                                                                              \
-  } while (0)
 
 static const uint64_t C = GATHER_CHUNK;
 static const uint64_t M = ~0ull;
@@ -199,11 +191,6 @@ int main() {
     for (int it = 0; it < 6; it++) check_layout(rng, (rng() % 5000) * 64 + res);
   for (uint64_t res = 0; res < 64; res++) check_layout(rng, res);  // (a store of less than one line)
   check_refusals();
-  if (g_fail) {
-    fprintf(stderr, "append_check: %d invariant(s) failed\n", g_fail);
-    return 1;
-  }
-  printf("append_check ok: chunk %llu, %llu entries, %llu units\n", (unsigned long long)C,
-         (unsigned long long)g_entries, (unsigned long long)g_units);
-  return 0;
+  return check_done("append_check", "chunk %llu, %llu entries, %llu units", (unsigned long long)C,
+                    (unsigned long long)g_entries, (unsigned long long)g_units);
 }

@@ -19,20 +19,13 @@
 
 #include <initializer_list>
 
+#include "check.h"
 #include "srd_crc.h"
 #include "srd_fin.h"
 
 using namespace srd;
 
-static int g_fail = 0;
 static uint64_t g_cases = 0;
-#define EXPECT(c)                                                                  \
-  do {                                                                             \
-    if (!(c)) {                                                                    \
-      if (g_fail < 20) fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #c); \
-      g_fail++;                                                                    \
-    }                                                                              \
-  } while (0)
 
 constexpr uint64_t NT = 26;  // tiles
 alignas(64) static uint8_t buf[NT * TILE];
@@ -180,10 +173,5 @@ int main() {
     buf[p] = keep;
   }
 
-  if (g_fail) {
-    fprintf(stderr, "fin_check: %d check(s) failed\n", g_fail);
-    return 1;
-  }
-  printf("fin_check ok: %llu cases\n", (unsigned long long)g_cases);
-  return 0;
+  return check_done("fin_check", "%llu cases", (unsigned long long)g_cases);
 }

@@ -22,19 +22,11 @@
 #include <random>
 #include <vector>
 
+#include "check.h"
 #include "srd_gather.h"
 #include "srd_segments.h"
 
 using namespace srd;
-
-static int g_fail = 0;
-#define EXPECT(c)                                                                  \
-  do {                                                                             \
-    if (!(c)) {                                                                    \
-      if (g_fail < 20) fprintf(stderr, "%s:%d: invariant failed: %s\n", __FILE__, __LINE__, #c); \
-      g_fail++;                                                                    \
-    }                                                                              \
-  } while (0)
 
 static const uint64_t C = GATHER_CHUNK;
 
@@ -184,11 +176,6 @@ int main() {
     check_crc2(t, big, 0, 64 * C);
     check_crc2(t, big, 0, 65 * C + 1);
   }
-  if (g_fail) {
-    fprintf(stderr, "gather_check: %d invariant(s) failed\n", g_fail);
-    return 1;
-  }
-  printf("gather_check ok: chunk %llu, %llu hits, %llu units, %llu CRCs\n", (unsigned long long)C,
-         (unsigned long long)g_hits, (unsigned long long)g_units, (unsigned long long)g_crcs);
-  return 0;
+  return check_done("gather_check", "chunk %llu, %llu hits, %llu units, %llu CRCs", (unsigned long long)C,
+                    (unsigned long long)g_hits, (unsigned long long)g_units, (unsigned long long)g_crcs);
 }

@@ -21,20 +21,12 @@
 #include <random>
 #include <vector>
 
+#include "check.h"
 #include "srd_host.h"
 
 extern "C" {
 #include "srd_oracle.h"
 }
-
-static int g_fail = 0;
-#define EXPECT(c)                                                      \
-  do {                                                                 \
-    if (!(c)) {                                                        \
-      fprintf(stderr, "%s:%d: invariant failed: %s\n", __FILE__, __LINE__, #c); \
-      g_fail = 1;                                                      \
-    }                                                                  \
-  } while (0)
 
 static void check_store(const uint8_t* f, uint64_t n) {
   // heap copy of exactly n bytes so ASan sees any read past the end
@@ -123,7 +115,5 @@ int main(int argc, char** argv) {
     check_store(m.data(), m.size());
   }
   for (int j = 0; j < 2000; j++) check_layout(rng);
-  if (g_fail) return 1;
-  printf("host_fuzz ok\n");
-  return 0;
+  return check_done("host_fuzz", nullptr);
 }

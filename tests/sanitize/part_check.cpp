@@ -8,6 +8,9 @@
 //   - part_table_ok accepts every table of the documented domain (drawn here
 //     from all of it: empty blocks at 0 and g - 1, runs of empty blocks,
 //     one-span blocks, blocks exactly at the bound) and refuses its borders.
+// The wave shares are every share set of test_scan_wave_shares; the bound is
+// the one the workspace is sized by; the tables' domain is the one
+// srd_ctx_set_scan_blocks documents.
 // Every valid table of the stores of up to 40 spans is enumerated.
 // Exit status 0 = no sanitizer report and every invariant held.
 #include <stdint.h>
@@ -18,19 +21,12 @@
 #include <random>
 #include <vector>
 
+#include "check.h"
 #include "srd_part.h"
 
 using namespace srd;
 
-static int g_fail = 0;
 static uint64_t g_cases = 0, g_spans = 0;
-#define EXPECT(c)                                                                  \
-  do {                                                                             \
-    if (!(c)) {                                                                    \
-      if (g_fail < 20) fprintf(stderr, "%s:%d: invariant failed: %s\n", __FILE__, __LINE__, #c); \
-      g_fail++;                                                                    \
-    }                                                                              \
-  } while (0)
 
 // the library's grid for ns resident spans of a 16-wave variant on 256 CUs (scan_grid)
 static uint32_t grid_of(uint64_t ns) { return (uint32_t)std::min<uint64_t>((ns + 15) / 16, 256); }
@@ -282,11 +278,6 @@ int main() {
     }
   }
   EXPECT(g_seen.empty0 && g_seen.empty_last && g_seen.empty_pair && g_seen.one_span && g_seen.at_bound);
-  if (g_fail) {
-    fprintf(stderr, "part_check: %d invariant failures\n", g_fail);
-    return 1;
-  }
-  printf("part_check ok: %llu partitions, %llu spans inverted\n", (unsigned long long)g_cases,
-         (unsigned long long)g_spans);
-  return 0;
+  return check_done("part_check", "%llu partitions, %llu spans inverted", (unsigned long long)g_cases,
+                    (unsigned long long)g_spans);
 }

@@ -27,54 +27,14 @@
 #include <string>
 #include <vector>
 
+#include "check.h"
 #include "srd_table.h"
 #include "srd_ttl.h"
 #include "srd_rows.h"
 
 using namespace srd;
 
-static int g_fail = 0;
-#define EXPECT(c)                                                                  \
-  do {                                                                             \
-    if (!(c)) {                                                                    \
-      if (g_fail < 20) fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #c); \
-      g_fail++;                                                                    \
-    }                                                                              \
-  } while (0)
-
-static uint64_t rng_state = 0x5EED0019ull;
-static uint64_t rnd() {  // splitmix64
-  uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-static void put64(std::vector<uint8_t>& f, uint64_t v) {
-  for (int k = 0; k < 8; k++) f.push_back((uint8_t)(v >> (8 * k)));
-}
-
-struct Ent {
-  uint64_t kh, meta, start;
-  bool tomb;
-};
-// the reference's append (data_store.rs:864-914): prepad to 64 (none for a
-// tombstone), payload, {key_hash, prev_offset = the tail before, crc}
-struct Store {
-  std::vector<uint8_t> f;
-  std::vector<Ent> ents;
-  void append(uint64_t len, uint64_t kh, bool tomb) {
-    const uint64_t tail = f.size();
-    if (!tomb) f.resize(tail + ((64 - (tail & 63)) & 63), 0);
-    const uint64_t st = f.size();
-    for (uint64_t i = 0; i < len; i++) f.push_back(tomb ? 0 : (uint8_t)(rnd() | 1));
-    const uint64_t meta = f.size();
-    put64(f, kh);
-    put64(f, tail);
-    for (int k = 0; k < 4; k++) f.push_back((uint8_t)rnd());
-    ents.push_back(Ent{kh, meta, st, tomb});
-  }
-};
+static SplitMix64 rnd{0x5EED0019ull};
 
 // rows_layout_kernel's decision for one query, on an exact-size heap copy of f[0 .. flen)
 struct Row {
@@ -83,21 +43,20 @@ struct Row {
 };
 static Row layout_at(const Table& t, const std::vector<uint8_t>& f, uint64_t flen, uint64_t q, const uint64_t* verify,
                      uint64_t row_cap) {
-  uint8_t* buf = new uint8_t[flen ? flen : 1];
-  if (flen) memcpy(buf, f.data(), flen);
-  uint64_t start = 0, end = 0;
-  const uint64_t p = table_get(t, q);
-  bool have = p != TBL_EMPTY;
-  if (have && verify) have = (p >> 48) == (*verify >> 48);
-  if (have) have = entry_range(flen ? buf : nullptr, flen, p & 0xFFFFFFFFFFFFull, &start, &end);
-  const RowVerdict v = rows_judge(start, end, have, row_cap);
-  delete[] buf;
-  return Row{v, v.status == SRD_GATHER_NONE ? 0 : start, v.status == SRD_GATHER_NONE ? 0 : end};
+  return with_exact_copy(f.data(), flen, [&](const uint8_t* buf) {
+    uint64_t start = 0, end = 0;
+    const uint64_t p = table_get(t, q);
+    bool have = p != TBL_EMPTY;
+    if (have && verify) have = (p >> 48) == (*verify >> 48);
+    if (have) have = entry_range(buf, flen, p & 0xFFFFFFFFFFFFull, &start, &end);
+    const RowVerdict v = rows_judge(start, end, have, row_cap);
+    return Row{v, v.status == SRD_GATHER_NONE ? 0 : start, v.status == SRD_GATHER_NONE ? 0 : end};
+  });
 }
 
 static void random_stores() {
   for (int round = 0; round < 30; round++) {
-    Store s;
+    Store s(rnd);
     const int n = 1 + (int)(rnd() % 40);
     std::vector<uint64_t> mem(table_bytes_for(n) / 8);
     Table t = table_view(mem.data(), mem.size() * 8);
@@ -105,7 +64,8 @@ static void random_stores() {
     for (int i = 0; i < n; i++) {
       const uint64_t kh = rnd();
       const bool tomb = rnd() % 8 == 0;
-      s.append(tomb ? 1 : 1 + rnd() % 300, kh, tomb);
+      if (tomb) s.tombstone(kh);
+      else s.plain(1 + rnd() % 300, kh);
       table_claim(t, kh, (kh >> 48 << 48) | s.ents.back().meta);
     }
     // one key removed: its slot keeps the key, the packed word is TBL_DELETED
@@ -161,8 +121,8 @@ static void judge_boundaries() {
 
 // the batch of kLens as rows: the units of the range view tile each delivered row exactly
 static void unit_tiling() {
-  Store s;
-  for (uint64_t len : kLens) s.append(len, rnd(), false);
+  Store s(rnd);
+  for (uint64_t len : kLens) s.plain(len, rnd());
   const uint64_t n = s.ents.size();
   for (uint64_t row_cap : {(uint64_t)64, C_, C_ + 16, 2 * C_ + 5, 3 * C_ + 48}) {
     for (uint64_t stride : {(row_cap + 15) & ~15ull, ((row_cap + 15) & ~15ull) + 16}) {
@@ -282,10 +242,5 @@ int main() {
   unit_tiling();
   refusals();
   workspace_monotone();
-  if (g_fail) {
-    fprintf(stderr, "rows_check: %d checks failed\n", g_fail);
-    return 1;
-  }
-  printf("rows_check ok\n");
-  return 0;
+  return check_done("rows_check", nullptr);
 }

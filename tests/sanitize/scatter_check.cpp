@@ -33,32 +33,14 @@
 #include <random>
 #include <vector>
 
+#include "check.h"
 #include "srd_scatter.h"
 
 using namespace srd;
 
-static int g_fail = 0;
-#define EXPECT(c)                                                                  \
-  do {                                                                             \
-    if (!(c)) {                                                                    \
-      if (g_fail < 20) fprintf(stderr, "%s:%d: invariant failed: %s\n", __FILE__, __LINE__, #c); \
-      g_fail++;                                                                    \
-    }                                                                              \
-  } while (0)
-
 static const uint64_t C = GATHER_CHUNK;
 static const uint64_t M = ~0ull;
 static const uint8_t FILL = 0xA5, GUARD = 0xEE;
-
-// CRC-32 (IEEE, reflected) bit by bit
-static uint32_t crc32_bitwise(const uint8_t* p, uint64_t n) {
-  uint32_t c = 0xFFFFFFFFu;
-  for (uint64_t i = 0; i < n; i++) {
-    c ^= p[i];
-    for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1)));
-  }
-  return ~c;
-}
 
 // what scatter_layout_kernel and the host compute for a batch
 struct Layout {
@@ -335,18 +317,6 @@ static void run_batch(const CrcTables& t, std::mt19937_64& rng, const std::vecto
   free(file);
 }
 
-static uint64_t pick_len(std::mt19937_64& rng) {
-  switch (rng() % 8) {
-    case 0: return 0;
-    case 1: return 1 + rng() % 17;
-    case 2: return 15 + rng() % 3;
-    case 3: return C - 16 + rng() % 33;
-    case 4: return C * (1 + rng() % 2) + rng() % 40;
-    case 5: return 4080 + rng() % 40;
-    default: return 1 + rng() % 9000;
-  }
-}
-
 static void check_random(const CrcTables& t, std::mt19937_64& rng) {
   std::vector<QuerySpec> spec;
   const uint64_t n = 1 + rng() % 10;
@@ -358,7 +328,7 @@ static void check_random(const CrcTables& t, std::mt19937_64& rng) {
     q.len = 0;
     const uint64_t k = 1 + rng() % 5;
     for (uint64_t j = 0; j < k; j++) {
-      q.segs.push_back(SegSpec{pick_len(rng), -1});
+      q.segs.push_back(SegSpec{pick_len(rng, C), -1});
       q.len += q.segs.back().len;
     }
     if (!q.len) { q.segs.back().len = 1 + rng() % 100; q.len = q.segs.back().len; }
@@ -499,12 +469,7 @@ int main() {
   for (int it = 0; it < 150; it++) check_random(t, rng);
   check_residues(t, rng);
   check_refusals();
-  if (g_fail) {
-    fprintf(stderr, "scatter_check: %d invariant(s) failed\n", g_fail);
-    return 1;
-  }
-  printf("scatter_check ok: chunk %llu, %llu queries, %llu segments, %llu units, %llu vector pieces, %llu pieces byte by byte\n",
-         (unsigned long long)C, (unsigned long long)g_queries, (unsigned long long)g_segs, (unsigned long long)g_units,
-         (unsigned long long)g_vec, (unsigned long long)g_bytewise);
-  return 0;
+  return check_done("scatter_check", "chunk %llu, %llu queries, %llu segments, %llu units, %llu vector pieces, %llu pieces byte by byte",
+                    (unsigned long long)C, (unsigned long long)g_queries, (unsigned long long)g_segs, (unsigned long long)g_units,
+                    (unsigned long long)g_vec, (unsigned long long)g_bytewise);
 }

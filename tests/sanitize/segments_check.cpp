@@ -7,7 +7,8 @@
 //     lies inside one segment, is at most SRD_GATHER_CHUNK long, and ends where
 //     the next unit's destination begins; every unit but a segment's first
 //     starts at a 16-byte boundary of the store;
-//   - a unit's descriptor never lets an aligned 16-byte load leave its segment;
+//   - a unit's descriptor never lets an aligned 16-byte load leave its segment,
+//     and the funnel of the loaded vectors gives the unit's bytes;
 //   - the same for the chunk units of the gather and the append (a whole range
 //     as one segment: the range view) at every start residue, with the pad
 //     count of a last unit;
@@ -28,19 +29,11 @@
 #include <random>
 #include <vector>
 
+#include "check.h"
 #include "srd_segments.h"
 #include "srd_host.h"
 
 using namespace srd;
-
-static int g_fail = 0;
-#define EXPECT(c)                                                                  \
-  do {                                                                             \
-    if (!(c)) {                                                                    \
-      if (g_fail < 20) fprintf(stderr, "%s:%d: invariant failed: %s\n", __FILE__, __LINE__, #c); \
-      g_fail++;                                                                    \
-    }                                                                              \
-  } while (0)
 
 static const uint64_t C = GATHER_CHUNK;
 static const uint64_t M = ~0ull;
@@ -88,18 +81,6 @@ static Batch device_layout(uint64_t tail, const std::vector<srd_segment>& segs, 
   b.units = b.upre[ns];
   if (n) b.tail_ok = append_new_tail(tail, b.coarse, b.pre[n - 1], len_last, &b.new_tail);
   return b;
-}
-
-static uint64_t pick_len(std::mt19937_64& rng) {
-  switch (rng() % 8) {
-    case 0: return 0;
-    case 1: return 1 + rng() % 17;
-    case 2: return 15 + rng() % 3;
-    case 3: return C - 16 + rng() % 33;
-    case 4: return C * (1 + rng() % 2) + rng() % 40;
-    case 5: return 4080 + rng() % 40;
-    default: return 1 + rng() % 9000;
-  }
 }
 
 // The streaming kernel's walk over a unit's frame, piece by piece (seg_frame,
@@ -154,7 +135,7 @@ static void check_tables(const CrcTables& t, std::mt19937_64& rng, uint64_t tail
     for (uint64_t j = 0; j < k; j++) {
       srd_segment g{};
       g.src = (uint32_t)(rng() % src.size());
-      g.len = pick_len(rng);
+      g.len = pick_len(rng, C);
       if (j == k - 1 && cat[i].empty() && !g.len) g.len = 1 + rng() % 100;  // (no empty entry here)
       if (g.len > src_lens[g.src]) g.len = src_lens[g.src];
       g.off = rng() % (src_lens[g.src] - g.len + 1);
@@ -487,12 +468,7 @@ int main() {
   check_chunk_units(rng);
   for (int it = 0; it < 100; it++) check_views(rng);
   check_refusals();
-  if (g_fail) {
-    fprintf(stderr, "segments_check: %d invariant(s) failed\n", g_fail);
-    return 1;
-  }
-  printf("segments_check ok: chunk %llu, %llu entries, %llu segments, %llu units, %llu chunk units, %llu units under both views\n",
-         (unsigned long long)C, (unsigned long long)g_entries, (unsigned long long)g_segs, (unsigned long long)g_units,
-         (unsigned long long)g_chunk_units, (unsigned long long)g_view_units);
-  return 0;
+  return check_done("segments_check", "chunk %llu, %llu entries, %llu segments, %llu units, %llu chunk units, %llu units under both views",
+                    (unsigned long long)C, (unsigned long long)g_entries, (unsigned long long)g_segs, (unsigned long long)g_units,
+                    (unsigned long long)g_chunk_units, (unsigned long long)g_view_units);
 }

@@ -21,26 +21,12 @@
 #include <unordered_set>
 #include <vector>
 
+#include "check.h"
 #include "srd_table.h"
 
 using namespace srd;
 
-static int g_fail = 0;
-#define EXPECT(c)                                                                  \
-  do {                                                                             \
-    if (!(c)) {                                                                    \
-      if (g_fail < 20) fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #c); \
-      g_fail++;                                                                    \
-    }                                                                              \
-  } while (0)
-
-static uint64_t rng_state = 0x5EEDull;
-static uint64_t rnd() {  // splitmix64
-  uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+static SplitMix64 rnd{0x5EEDull};
 
 // A table in host memory, maintained the way the apply maintains the device's:
 // a key with a slot (live or deleted) is stored into it, a new key is admitted
@@ -145,7 +131,7 @@ static void full_check(uint64_t cap) {
 }
 
 static void random_run(uint64_t cap, uint64_t seed) {
-  rng_state = seed;
+  rnd.state = seed;
   HostTable h(cap / 2);
   EXPECT(h.cap() == cap);
   std::vector<uint64_t> universe = {0ull, ~0ull};
@@ -213,10 +199,5 @@ int main() {
     random_run(cap, 0xC0FFEE + cap);
   }
   size_check();
-  if (g_fail) {
-    fprintf(stderr, "table_check: %d checks failed\n", g_fail);
-    return 1;
-  }
-  printf("table_check ok\n");
-  return 0;
+  return check_done("table_check", nullptr);
 }

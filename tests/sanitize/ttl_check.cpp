@@ -31,75 +31,29 @@
 #include <map>
 #include <vector>
 
+#include "check.h"
 #include "srd_table.h"
 #include "srd_ttl.h"
 
 using namespace srd;
 
-static int g_fail = 0;
-#define EXPECT(c)                                                                  \
-  do {                                                                             \
-    if (!(c)) {                                                                    \
-      if (g_fail < 20) fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #c); \
-      g_fail++;                                                                    \
-    }                                                                              \
-  } while (0)
+static SplitMix64 rnd{0x5EED0018ull};
 
-static uint64_t rng_state = 0x5EED0018ull;
-static uint64_t rnd() {  // splitmix64
-  uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-static void put64(std::vector<uint8_t>& f, uint64_t v) {
-  for (int k = 0; k < 8; k++) f.push_back((uint8_t)(v >> (8 * k)));
-}
-
-// what the model knows about an entry it wrote
-struct Ent {
-  uint64_t meta, start;  // metadata offset, payload start
-  bool tomb;
-};
-
-// the reference's append (data_store.rs:864-914): prepad to 64 (none for a
-// tombstone), payload, {key_hash, prev_offset = the tail before, crc}
-struct Store {
-  std::vector<uint8_t> f;
-  std::vector<Ent> ents;
-  void append(const std::vector<uint8_t>& payload, uint64_t kh, bool tomb) {
-    const uint64_t tail = f.size();
-    if (!tomb) f.resize(tail + ((64 - (tail & 63)) & 63), 0);
-    const uint64_t st = f.size();
-    f.insert(f.end(), payload.begin(), payload.end());
-    const uint64_t meta = f.size();
-    put64(f, kh);
-    put64(f, tail);
-    for (int k = 0; k < 4; k++) f.push_back((uint8_t)rnd());  // (the rule reads no checksum)
-    ents.push_back(Ent{meta, st, tomb});
-  }
+// a store of check.h's model with TTL entries: the payload is the expiry's 8
+// bytes and the value
+struct TtlStore : Store {
+  TtlStore() : Store(rnd) {}
   void ttl(uint64_t expiry, uint64_t value_len, uint64_t kh) {
     std::vector<uint8_t> p;
     put64(p, expiry);
     for (uint64_t i = 0; i < value_len; i++) p.push_back((uint8_t)rnd());
     append(p, kh, false);
   }
-  void plain(uint64_t len, uint64_t kh) {
-    std::vector<uint8_t> p;
-    for (uint64_t i = 0; i < len; i++) p.push_back((uint8_t)(rnd() | 1));
-    append(p, kh, false);
-  }
-  void tombstone(uint64_t kh) { append({0}, kh, true); }
 };
 
 // ttl_judge on an exact-size heap copy of f[0 .. flen)
 static TtlVerdict judge_at(const std::vector<uint8_t>& f, uint64_t flen, uint64_t off, uint64_t now) {
-  uint8_t* buf = new uint8_t[flen ? flen : 1];
-  if (flen) memcpy(buf, f.data(), flen);
-  const TtlVerdict v = ttl_judge(flen ? buf : nullptr, flen, off, now);
-  delete[] buf;
-  return v;
+  return with_exact_copy(f.data(), flen, [&](const uint8_t* p) { return ttl_judge(p, flen, off, now); });
 }
 
 static TtlVerdict model(const Store& s, const Ent& e, uint64_t flen, uint64_t now) {
@@ -133,7 +87,7 @@ static void check_store(const Store& s, uint64_t now) {
 static void random_stores() {
   const uint64_t now = 1700000000ull;
   for (int round = 0; round < 40; round++) {
-    Store s;
+    TtlStore s;
     const int n = 1 + (int)(rnd() % 40);
     for (int i = 0; i < n; i++) {
       const uint64_t r = rnd() % 10;
@@ -153,7 +107,7 @@ static void random_stores() {
 static void boundaries() {
   const uint64_t nows[] = {0, 1, 1700000000ull, ~0ull - 1, ~0ull};
   for (uint64_t now : nows) {
-    Store s;
+    TtlStore s;
     const uint64_t exps[] = {now - 1, now, now + 1, 0, ~0ull};
     for (uint64_t x : exps) s.ttl(x, 5, rnd());
     for (size_t i = 0; i < 5; i++) {
@@ -168,7 +122,7 @@ static void boundaries() {
   }
   // expiry == now is expired, now + 1 is live (away from the wrap)
   {
-    Store s;
+    TtlStore s;
     s.ttl(1000, 0, 1);
     EXPECT(judge_at(s.f, s.f.size(), s.ents[0].meta, 999).status == TTL_LIVE);
     EXPECT(judge_at(s.f, s.f.size(), s.ents[0].meta, 1000).status == TTL_EXPIRED);
@@ -178,7 +132,7 @@ static void boundaries() {
 
 static void lengths() {
   const uint64_t now = 50;
-  Store s;
+  TtlStore s;
   s.plain(1, 1);  // (a single non-zero byte: not a tombstone)
   s.plain(7, 2);
   s.ttl(100, 0, 3);  // 8 bytes: an empty value
@@ -200,7 +154,7 @@ static void lengths() {
 static void tombstones_and_ranges() {
   const uint64_t now = 50;
   {
-    Store s;
+    TtlStore s;
     s.tombstone(9);  // at offset 0: prev_offset 0, the NULL byte at 0, metadata at 1
     s.ttl(100, 3, 1);
     s.tombstone(1);
@@ -212,7 +166,7 @@ static void tombstones_and_ranges() {
   // prev_offset values that no store holds: near 2^64, equal to and above the metadata offset
   const uint64_t prevs[] = {~0ull, ~0ull - 62, ~0ull - 63, 1ull << 63, 64, 65, 84, 1000};
   for (uint64_t prev : prevs) {
-    Store s;
+    TtlStore s;
     s.ttl(100, 3, 1);
     const uint64_t meta = s.ents[0].meta;
     for (int k = 0; k < 8; k++) s.f[meta + 8 + k] = (uint8_t)(prev >> (8 * k));
@@ -238,7 +192,7 @@ static void expiry_add() {
 // the resolve's per-query path on a host table
 static void through_the_table() {
   const uint64_t now = 1000;
-  Store s;
+  TtlStore s;
   std::vector<uint64_t> mem(table_bytes_for(8) / 8);
   Table t = table_view(mem.data(), mem.size() * 8);
   for (uint64_t i = 0; i < (1ull << t.log2cap); i++) t.packed[i] = TBL_EMPTY;
@@ -320,10 +274,5 @@ int main() {
   expiry_add();
   through_the_table();
   evict_order();
-  if (g_fail) {
-    fprintf(stderr, "ttl_check: %d checks failed\n", g_fail);
-    return 1;
-  }
-  printf("ttl_check ok\n");
-  return 0;
+  return check_done("ttl_check", nullptr);
 }

@@ -1,10 +1,10 @@
 """CPU-side checks of the device-append boundary (no GPU calls): the header,
 the binding list and the built library agree on srd_batch_append_device, its
-14 arguments and its flag; the Python layer carries the documented names; and
+14 arguments and its flag; and the Python layer carries the documented names.
 csrc/srd_append.h (the range rule, the layout by one exclusive sum and the
-refusals that the kernels and the host glue run) holds its invariants against
-srd_batch_layout as a stand-alone host program under ASan + UBSan
-(tests/sanitize_append/append_check.cpp)."""
+refusals that the kernels and the host glue run) is checked against
+srd_batch_layout by a stand-alone host program under ASan + UBSan,
+tests/sanitize/append_check.cpp, which tests/test_sanitized_rules.py runs."""
 import inspect
 import os
 import re
@@ -60,18 +60,3 @@ def test_python_interface_names():
     assert list(inspect.signature(D.batch_copy).parameters) == ["self", "keys", "target"]
     assert list(inspect.signature(D.batch_transfer).parameters) == ["self", "keys", "target"]
     assert list(inspect.signature(D.batch_rename).parameters) == ["self", "old_keys", "new_keys"]
-
-
-def test_append_arithmetic_sanitized():
-    """csrc/srd_append.h as a plain executable under ASan + UBSan (nothing is
-    loaded into Python): the layout by one exclusive sum equals srd_batch_layout's
-    for seeded random length vectors at every start tail residue 0..63; zero
-    lengths, ranges outside the blob (wrap-around values near 2^64) and the 2^48
-    bound are refused, the first refused entry deciding; the units tile every
-    entry exactly once with 64-aligned destinations."""
-    d = os.path.join(ROOT, "tests", "sanitize_append")
-    subprocess.check_call(["make", "-s", "-C", d])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([os.path.join(d, "build", "append_check")], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0 and "append_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
-    assert "chunk %d," % srd_amd.GATHER_CHUNK in p.stdout

@@ -4,7 +4,7 @@ arguments and srd_compact_stats; the header states what the new table's `used`
 count is and how the call synchronises; and the Python layer carries the
 documented session methods with their signatures and defaults.  (The change
 puts no host-callable arithmetic into a header -- the layout is srd_append.h's,
-which tests/sanitize_append checks -- so there is no stand-alone sanitizer
+which tests/sanitize/append_check.cpp checks -- so there is no stand-alone sanitizer
 program of its own.)"""
 import ctypes as C
 import inspect

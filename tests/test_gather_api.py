@@ -1,9 +1,10 @@
 """CPU-side checks of the payload-gather boundary (no GPU calls): the header,
 the binding list and the built library agree on srd_payload_gather_device, its
-14 arguments and its constants; the Python classes carry the documented names;
-and csrc/srd_gather.h (the range rule, the unit / chunk arithmetic and the CRC
-combine the kernels run) holds its invariants as a stand-alone host program
-under ASan + UBSan (tests/sanitize_gather/gather_check.cpp)."""
+14 arguments and its constants; and the Python classes carry the documented
+names.  csrc/srd_gather.h (the range rule, the unit / chunk arithmetic and the
+CRC combine the kernels run) is checked by a stand-alone host program under
+ASan + UBSan, tests/sanitize/gather_check.cpp, which
+tests/test_sanitized_rules.py runs."""
 import os
 import re
 import subprocess
@@ -58,19 +59,3 @@ def test_python_interface_names():
     r = srd_amd.GatherResult(None, [0, 64, 64, 64], [3, 0, 0], [srd_amd.GATHER_BAD_CRC, srd_amd.GATHER_NONE,
                                                                 srd_amd.GATHER_BAD_RANGE], [1, 0, 0])
     assert r.is_valid_checksum() == [False, None, None] and len(r) == 3
-
-
-def test_gather_arithmetic_sanitized():
-    """csrc/srd_gather.h as a plain executable under ASan + UBSan (nothing is
-    loaded into Python): the units tile every hit exactly once and unit -> hit
-    inverts; the CRC combined from per-unit raw CRCs (every unit's term, XORed
-    as the combine's 64 lanes stride over the units, for the chunk cut and for
-    a cut at destination residue 5) equals a byte-wise CRC-32 for the GPU
-    tests' length set and seeded random lengths up to 5 chunks; the offsets are
-    the exclusive sum of the padded lengths; the range rule's borders."""
-    d = os.path.join(ROOT, "tests", "sanitize_gather")
-    subprocess.check_call(["make", "-s", "-C", d])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([os.path.join(d, "build", "gather_check")], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0 and "gather_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
-    assert "chunk %d," % srd_amd.GATHER_CHUNK in p.stdout

@@ -1,7 +1,9 @@
 """CPU checks of the host side of the boundary (no GPU calls):
   - the ASan/UBSan build of the host parsers of untrusted store bytes
     (srd_host.cpp: srd_shard_cuts, srd_batch_layout) and of the oracle, over
-    the golden fixtures (garbage included), their mutations and random bytes;
+    the golden fixtures (garbage included), their mutations and random bytes
+    (tests/sanitize/host_fuzz.cpp, run as tests/test_sanitized_rules.py runs
+    the rule checks);
   - the compiled C caller of include/srd_amd.h builds and its struct layout
     equals the ctypes mirror and the #[repr(C)] Rust struct of INTEGRATION.md;
   - the single-process multi-GPU open's composition + latest-wins index merge
@@ -19,60 +21,15 @@ import pytest
 
 import oracle as O
 import srd_amd as S
+from test_sanitized_rules import run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_sanitizer_harness():
-    d = os.path.join(ROOT, "tests", "sanitize")
-    subprocess.check_call(["make", "-s", "-C", d])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     fx = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "*.bin")))
     assert any("garbage" in f for f in fx)
-    p = subprocess.run([os.path.join(d, "build", "host_fuzz")] + fx, capture_output=True, text=True, env=env,
-                       timeout=600)
-    assert p.returncode == 0 and "host_fuzz ok" in p.stdout, p.stderr[-3000:]
-
-
-def test_scan_partition_arithmetic_sanitized():
-    """csrc/srd_part.h (the scan's block / wave partition and its inverse, the code the kernels run) as a
-    stand-alone host program under ASan + UBSan: the wave ranges tile the resident spans, part_span_wave
-    inverts them for every span, no wave exceeds the bound the workspace is sized by -- over seeded random
-    stores, every wave-share set of test_scan_wave_shares and block-start tables from the whole domain of
-    srd_ctx_set_scan_blocks (tests/sanitize/part_check.cpp)."""
-    d = os.path.join(ROOT, "tests", "sanitize")
-    subprocess.check_call(["make", "-s", "-C", d, "build/part_check"])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([os.path.join(d, "build", "part_check")], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0 and "part_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
-
-
-def test_finalize_rule_sanitized():
-    """csrc/srd_fin.h (the finalize rule: an entry's CRC from the scan's pieces, the code finalize_core,
-    finalize_in and the slow path run) as a stand-alone host program under ASan + UBSan: over every start-line and
-    metadata-line class and 0..22 whole tiles between them the serial and the grouped crc_from_pieces equal a
-    byte-wise CRC-32; short entries; every fin_pieces branch resolves the byte-wise suffix or leaves the piece
-    missing; fin_route sends exactly the entries with a missing piece or more than LONG_TILES whole tiles to the
-    slow list (tests/sanitize/fin_check.cpp)."""
-    d = os.path.join(ROOT, "tests", "sanitize")
-    subprocess.check_call(["make", "-s", "-C", d, "build/fin_check"])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([os.path.join(d, "build", "fin_check")], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0 and "fin_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
-
-
-def test_index_table_rule_sanitized():
-    """csrc/srd_table.h (the device index table: probe, claim, slot states, size arithmetic -- the code the table's
-    kernels run, the claim's CAS as a plain compare-and-store) as a stand-alone host program under ASan + UBSan,
-    single-threaded against a std::unordered_map: a probe chain of 12 keys that wraps from slot 63 to slot 0, a
-    delete in its middle and the revival into the same slot, key hashes 0 and 2^64 - 1, an absent key's probe past
-    deleted slots, seeded runs of 10 000 operations at capacities 64 and 1024 that reach capacity / 2 non-empty slots
-    and meet the refusal there, and the capacity / log2cap / table_ok arithmetic (tests/sanitize/table_check.cpp)."""
-    d = os.path.join(ROOT, "tests", "sanitize")
-    subprocess.check_call(["make", "-s", "-C", d, "build/table_check"])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([os.path.join(d, "build", "table_check")], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0 and "table_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
+    run_sanitized("host_fuzz", fx)
 
 
 def _abi_check_bin():

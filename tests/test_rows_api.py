@@ -2,11 +2,11 @@
 binding list, the built library and the ctypes argument lists agree on the two
 new entries and their 64-bit parameters; SRD_ROWS_TOO_LONG is 5 in the header
 and the module and the gather's 0 / 1 / 2 are unchanged; the header says that
-the call does not wait and what the reserve call is for; the Python layer
-carries the documented names; and csrc/srd_rows.h over csrc/srd_ttl.h /
-srd_table.h / srd_segments.h (the code the kernels and the host glue run) holds
-its contract as a stand-alone host program under ASan + UBSan
-(tests/sanitize_rows/rows_check.cpp)."""
+the call does not wait and what the reserve call is for; and the Python layer
+carries the documented names.  csrc/srd_rows.h over csrc/srd_ttl.h /
+srd_table.h / srd_segments.h (the code the kernels and the host glue run) is
+checked by a stand-alone host program under ASan + UBSan,
+tests/sanitize/rows_check.cpp, which tests/test_sanitized_rules.py runs."""
 import ctypes as C
 import inspect
 import os
@@ -150,20 +150,3 @@ def test_rows_result_waits_lazily_and_once():
     assert r.too_long() == [(3, 99)]
     assert r.payloads() == [None, bytes((1, 2, 3)), bytes([7] * 8), None]
     assert sorted(calls) == ["lens", "out", "status"]
-
-
-def test_rows_rule_sanitized():
-    """csrc/srd_rows.h over srd_ttl.h / srd_table.h / srd_segments.h as a plain
-    executable under ASan + UBSan (nothing is loaded into Python): the layout's
-    per-query decision over seeded random stores in exact-size heap buffers
-    (tombstones, removed keys, tag mismatch, offsets at and above file_len);
-    rows_judge at row_cap = len - 1, len, len + 1 for lengths 1 .. 2 C + 5; the
-    units of the range view with off[i] = i * stride tiling every delivered row
-    exactly, none crossing into a neighbouring row, at strides row_cap and
-    row_cap + 16; the refusal arithmetic at 2^31, 2^32 and wrap-around values;
-    workspace sizes monotone in (n, row_cap)."""
-    d = os.path.join(ROOT, "tests", "sanitize_rows")
-    subprocess.check_call(["make", "-s", "-C", d])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([os.path.join(d, "build", "rows_check")], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0 and "rows_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])

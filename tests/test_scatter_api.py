@@ -2,12 +2,12 @@
 binding list and the built library agree on srd_payload_scatter_device, its 16
 parameters and their widths; SRD_SCATTER_BAD_LENGTH is 4 in the header and the
 module; the header names the reference's EntryStream and says that the call
-waits once; the Python layer carries the documented names; and
+waits once; and the Python layer carries the documented names.
 csrc/srd_scatter.h with the scatter view of csrc/srd_segments.h (the entry
 walk, the unit cut at the destination's residue, the unit descriptor, the
 streaming kernel's frame and the CRC combine that the kernels and the host
-glue run) holds its invariants as a stand-alone host program under ASan +
-UBSan (tests/sanitize_scatter/scatter_check.cpp)."""
+glue run) is checked by a stand-alone host program under ASan + UBSan,
+tests/sanitize/scatter_check.cpp, which tests/test_sanitized_rules.py runs."""
 import ctypes as C
 import inspect
 import os
@@ -112,22 +112,3 @@ def test_scatter_result_rule():
     assert r.is_valid_checksum() == [True, False, None, None] == S.GatherResult(None, None, None, st, None).is_valid_checksum()
     with pytest.raises(ValueError):
         S.ScatterResult(np.array([S.GATHER_OK, S.SCATTER_BAD_LENGTH], np.uint8), np.zeros(2, np.uint32)).is_valid_checksum()
-
-
-def test_scatter_arithmetic_sanitized():
-    """csrc/srd_scatter.h and unit_of<ScatterView> as a plain executable under
-    ASan + UBSan (nothing is loaded into Python): over seeded random batches and
-    all 256 residue pairs the units tile each OK payload once and in order, each
-    inside one destination segment and at most a chunk long; the layout's unit
-    counts equal the units'; the streaming kernel's piece walk over host buffers
-    with guard bytes loads nothing outside [start, end), stores nothing outside
-    its segment and its funnel gives the unit's bytes; the XOR of the units'
-    terms is a bitwise CRC-32 of the payload; every refusal the arithmetic
-    decides is taken, the first query deciding, with values near 2^64; sums one
-    short and one over are BAD_LENGTH."""
-    d = os.path.join(ROOT, "tests", "sanitize_scatter")
-    subprocess.check_call(["make", "-s", "-C", d])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([os.path.join(d, "build", "scatter_check")], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0 and "scatter_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
-    assert "chunk %d," % srd_amd.GATHER_CHUNK in p.stdout

@@ -2,11 +2,12 @@
 the binding list and the built library agree on
 srd_batch_append_segments_device, its parameters and their widths, and on
 srd_segment's layout (a C translation unit of static assertions and the ctypes
-structure); the header says that the call waits twice; the Python layer carries
-the documented names; and csrc/srd_segments.h (the table rule, the unit cut,
-the unit descriptor, the streaming kernel's frame and the CRC combine that the
-kernels and the host glue run) holds its invariants as a stand-alone host
-program under ASan + UBSan (tests/sanitize_segments/segments_check.cpp)."""
+structure); the header says that the call waits twice; and the Python layer
+carries the documented names.  csrc/srd_segments.h (the table rule, the unit
+cut, the unit descriptor, the streaming kernel's frame and the CRC combine that
+the kernels and the host glue run) is checked by a stand-alone host program
+under ASan + UBSan, tests/sanitize/segments_check.cpp, which
+tests/test_sanitized_rules.py runs."""
 import ctypes as C
 import inspect
 import os
@@ -93,20 +94,3 @@ def test_python_interface_names():
     assert list(inspect.signature(D.write_stream).parameters) == ["self", "key", "segments"]
     for name in ("batch_write_stream_with_key_hashes", "batch_write_stream", "write_stream_with_key_hash", "write_stream"):
         assert "data_store.rs" in getattr(D, name).__doc__, name  # named after the reference method it replaces
-
-
-def test_segments_arithmetic_sanitized():
-    """csrc/srd_segments.h as a plain executable under ASan + UBSan (nothing is
-    loaded into Python): over seeded random segment tables the units tile every
-    entry's bytes once and in order, each inside one segment and at most a chunk
-    long; the streaming kernel's frame never lets an aligned load leave its
-    segment and its funnel gives the unit's bytes; the XOR of the units' terms is
-    the CRC-32 of the concatenation (0xCBF43926 included); the entry layout equals
-    srd_batch_layout's at every tail residue; every refusal the arithmetic decides
-    is taken, the first entry deciding, with wrap-around values near 2^64."""
-    d = os.path.join(ROOT, "tests", "sanitize_segments")
-    subprocess.check_call(["make", "-s", "-C", d])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([os.path.join(d, "build", "segments_check")], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0 and "segments_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
-    assert "chunk %d," % srd_amd.GATHER_CHUNK in p.stdout

@@ -2,11 +2,11 @@
 binding list, the built library and the ctypes argument lists agree on every
 new entry and its parameter count; the four statuses are 0..3 in the header and
 the module; the header names the reference code it replaces and says what each
-call reads, writes and waits for; the Python layer carries the documented
-names; and csrc/srd_ttl.h over csrc/srd_table.h (the range rule, ttl_judge, the
+call reads, writes and waits for; and the Python layer carries the documented
+names.  csrc/srd_ttl.h over csrc/srd_table.h (the range rule, ttl_judge, the
 saturating expiry, eviction's choice -- the code the kernels and the host glue
-run) holds its contract as a stand-alone host program under ASan + UBSan
-(tests/sanitize_ttl/ttl_check.cpp)."""
+run) is checked by a stand-alone host program under ASan + UBSan,
+tests/sanitize/ttl_check.cpp, which tests/test_sanitized_rules.py runs."""
 import ctypes as C
 import inspect
 import os
@@ -150,20 +150,3 @@ def test_expiry_saturates_and_result_rule():
                        np.array([S.GATHER_NONE, S.GATHER_OK], np.uint8), np.zeros(2, np.uint32))
     r = S.TtlReadResult(np.array([S.TTL_EXPIRED, S.TTL_LIVE], np.uint8), np.array([5, 99], np.uint64), g)
     assert len(r) == 2 and r.values() == [None, b"abc"] and r.is_valid_checksum() == [None, True] and r.n_evicted == 0
-
-
-def test_ttl_rule_sanitized():
-    """csrc/srd_ttl.h and csrc/srd_table.h as a plain executable under ASan +
-    UBSan (nothing is loaded into Python): ttl_judge over seeded random stores
-    in exact-size heap buffers, at every truncation around each entry's
-    metadata, reads nothing outside [0, file_len) and gives the contract's
-    status, range and expiry; expiry = now - 1, now, now + 1, 0 and 2^64 - 1;
-    payloads of 1, 7, 8 and 9 bytes; tombstones, offsets out of range, a record
-    ending exactly at file_len, prev_offset values near 2^64; the saturating
-    add; absent and removed keys through the table; eviction's one tombstone
-    per distinct expired key in batch order of its last expired query."""
-    d = os.path.join(ROOT, "tests", "sanitize_ttl")
-    subprocess.check_call(["make", "-s", "-C", d])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([os.path.join(d, "build", "ttl_check")], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0 and "ttl_check ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
