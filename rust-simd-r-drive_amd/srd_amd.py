@@ -1508,7 +1508,12 @@ class DeviceIndex:
         delivered (GATHER_NONE, ROWS_TOO_LONG) is left exactly as it was.
         The stream rule: the call runs on torch's CURRENT stream.  Outside a
         capture that stream first waits in-stream (an event) for the context
-        stream, so it sees what the library wrote before.  Under capture
+        stream, so it sees what the library wrote before.  torch's default
+        stream has the handle 0, which the library reads as "the context
+        stream": the call then runs on the context stream between two events
+        -- that stream waits for torch's, torch's waits for the read -- so work
+        ordered behind the read on torch's stream, and a host wait for that
+        stream, see the results all the same.  Under capture
         (torch.cuda.is_current_stream_capturing()) no cross-stream wait is issued:
         the caller has waited for the context stream (DeviceStore.sync) before
         capturing, and has called Context.reserve_rows(n, row_cap) -- a capture
@@ -1538,12 +1543,18 @@ class DeviceIndex:
         res = RowsResult(out, lens, status, crc, counts, cur)
         if not n:
             return res
-        if not torch.cuda.is_current_stream_capturing():
-            cur.wait_stream(torch.cuda.ExternalStream(self.ctx.stream, device=dev))
+        on_ctx = cur.cuda_stream == 0  # (the default stream cannot be named to the library: NULL is the context's)
+        lib_stream = torch.cuda.ExternalStream(self.ctx.stream, device=dev)
+        if on_ctx:
+            lib_stream.wait_stream(cur)
+        elif not torch.cuda.is_current_stream_capturing():
+            cur.wait_stream(lib_stream)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         _check(lib().srd_read_rows_device(self.ctx.h, p(self.table), self.nbytes, C.c_void_p(d_file), file_len, p(q), p(v),
                                           n, p(out), out.stride(0), out.shape[1], p(lens), p(status), p(crc), p(counts), 0,
-                                          C.c_void_p(cur.cuda_stream)))
+                                          C.c_void_p(self.ctx.stream if on_ctx else cur.cuda_stream)))
+        if on_ctx:
+            cur.wait_stream(lib_stream)
         res._keep = (q, v)  # (temporaries of this call: torch's allocator reuses them in stream order)
         return res
 
@@ -1840,8 +1851,9 @@ class DeviceStore:
     # -- copy / transfer / rename (data_store.rs:941-984): write_stream of the read entry ---
 
     def _entries_of(self, keys, missing: str):
-        """The payload ranges of `keys` as device tensors (hashes, start, length),
-        every read verified by its key's own tag; KeyError for a key that reads as None."""
+        """The payload ranges of `keys` as device tensors (hashes, start, length)
+        and the lengths on the host, every read verified by its key's own tag;
+        KeyError for a key that reads as None."""
         keys = [bytes(k) for k in keys]
         if len(set(keys)) != len(keys):
             raise ValueError("Duplicate keys in one batch.")
@@ -1852,7 +1864,7 @@ class DeviceStore:
         for k, a, b in zip(keys, hs, he):
             if a == b:
                 raise KeyError(f"{missing}: {k!r}")
-        return _keep[0], st, en - st
+        return _keep[0], st, en - st, he - hs
 
     def _append_from(self, src: "DeviceStore", d_hashes, st, lens) -> int:
         """write_stream_with_key_hash of src's entries at [st, st + lens) into this
@@ -1874,17 +1886,29 @@ class DeviceStore:
             raise ValueError("Cannot copy entry to the same storage. Use `rename` instead.")
         if not len(keys):
             return target._tail
-        h, st, lens = self._entries_of(keys, "Key not found")
-        return target._append_from(self, h, st, lens)
+        return target._append_from(self, *self._entries_of(keys, "Key not found")[:3])
 
     def batch_transfer(self, keys, target: "DeviceStore") -> int:
-        """transfer (data_store.rs:981-984): copy, then delete here.  Returns this store's new tail."""
-        self.batch_copy(keys, target)
-        return self.batch_delete(keys) if len(keys) else self._tail
+        """transfer (data_store.rs:981-984): copy, then delete here.  Returns this
+        store's new tail.  The whole transfer or nothing: once the keys are
+        resolved (copy's errors come first: the same storage, a duplicate, a
+        missing key), tombstones that would end beyond this store's capacity
+        raise ValueError before anything is copied."""
+        if target is self or target.buf.data_ptr() == self.buf.data_ptr():
+            raise ValueError("Cannot copy entry to the same storage. Use `rename` instead.")
+        if not len(keys):
+            return self._tail
+        h, st, lens, _hl = self._entries_of(keys, "Key not found")
+        if padded_size(self._tail + 21 * len(keys)) > self.buf.numel():
+            raise ValueError("the tombstones end beyond the store's capacity")
+        target._append_from(self, h, st, lens)
+        return self.batch_delete(keys)
 
     def batch_rename(self, old_keys, new_keys) -> int:
         """rename (data_store.rs:941-958) of every pair: the old entries appended
-        under the new keys' hashes, then the old keys deleted.  Returns the new tail."""
+        under the new keys' hashes, then the old keys deleted.  Returns the new
+        tail.  The whole rename or nothing: entries whose tombstones would end
+        beyond the capacity raise ValueError before anything is appended."""
         _same_len(old_keys, new_keys, "old and new keys")
         old_keys, new_keys = [bytes(k) for k in old_keys], [bytes(k) for k in new_keys]
         if any(a == b for a, b in zip(old_keys, new_keys)):
@@ -1893,7 +1917,12 @@ class DeviceStore:
             raise ValueError("Duplicate keys in one batch.")
         if not old_keys:
             return self._tail
-        _h, st, lens = self._entries_of(old_keys, "Old key not found")
+        _h, st, lens, hl = self._entries_of(old_keys, "Old key not found")
+        tail = self._tail
+        for n in hl:  # each payload at the next 64-byte boundary, then its 20 metadata bytes
+            tail = ((tail + 63) & ~63) + int(n) + 20
+        if padded_size(tail + 21 * len(old_keys)) > self.buf.numel():
+            raise ValueError("the renamed entries and their tombstones end beyond the store's capacity")
         self._append_from(self, self.index._as_dev(compute_hash_batch(new_keys, self.ctx)), st, lens)
         return self.batch_delete(old_keys)
 
